@@ -1179,6 +1179,15 @@ torch::Tensor& zero_page(const torch::Device& dev, torch::ScalarType st) {
   return it->second;
 }
 
+// The TN kernels stage 8-element (16 B) column groups.  With a column count
+// that is not a multiple of 8 a row's last group runs into the next row and,
+// on the last row, past the end of the buffer — pad such operands with zero
+// columns (the callers slice the result back).
+torch::Tensor pad_cols8(const torch::Tensor& t) {
+  const int64_t pad = (8 - t.size(-1) % 8) % 8;
+  return pad ? torch::constant_pad_nd(t, {0, pad}) : t;
+}
+
 struct NtExtras {
   float* stats_ws = nullptr;  // [2*nblocks][N], pre-zeroed
   int ws_nblocks = 0;
@@ -1510,6 +1519,10 @@ torch::Tensor bmm_tn_bf16(torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(A.is_contiguous() && B.is_contiguous());
   const bool batched = A.dim() == 3;
   TORCH_CHECK(!batched || B.dim() == 3);
+  if (A.size(-1) % 8 || B.size(-1) % 8) {
+    auto C = bmm_tn_bf16(pad_cols8(A), pad_cols8(B));
+    return C.narrow(-2, 0, A.size(-1)).narrow(-1, 0, B.size(-1)).contiguous();
+  }
   long long bsz = batched ? A.size(0) : 1;
   int M = (int)A.size(batched ? 1 : 0), I = (int)A.size(batched ? 2 : 1);
   int J = (int)B.size(batched ? 2 : 1);
@@ -1618,6 +1631,11 @@ torch::Tensor bmm_tn_bf16(torch::Tensor A, torch::Tensor B) {
 std::vector<torch::Tensor> bmm_tn_bias_bf16(torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2);
   TORCH_CHECK(A.is_contiguous() && B.is_contiguous());
+  if (A.size(1) % 8 || B.size(1) % 8) {
+    auto r = bmm_tn_bias_bf16(pad_cols8(A), pad_cols8(B));
+    return {r[0].narrow(0, 0, A.size(1)).narrow(1, 0, B.size(1)).contiguous(),
+            r[1].narrow(0, 0, A.size(1)).contiguous()};
+  }
   int M = (int)A.size(0), I = (int)A.size(1);
   int J = (int)B.size(1);
   TORCH_CHECK((int)B.size(0) == M);
