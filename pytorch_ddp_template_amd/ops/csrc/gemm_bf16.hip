@@ -2051,6 +2051,14 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
 torch::Tensor conv2d_wgrad_bf16(torch::Tensor dy, torch::Tensor x,
                                 int64_t stride, int64_t pad, int64_t R,
                                 int64_t S) {
+  // every wgrad kernel stages dy in 8-channel (16 B) groups guarded by the
+  // group's first channel only: pad Kout to a multiple of 8 (see pad_cols8)
+  // and slice the zero rows off dw
+  if (dy.size(3) % 8 != 0) {
+    const int64_t Kout = dy.size(3);
+    auto dw = conv2d_wgrad_bf16(pad_cols8(dy), x, stride, pad, R, S);
+    return dw.narrow(0, 0, Kout).contiguous();
+  }
   int N = (int)x.size(0), H = (int)x.size(1), W = (int)x.size(2),
       Cin = (int)x.size(3);
   int HO = (int)dy.size(1), WO = (int)dy.size(2), Kout = (int)dy.size(3);

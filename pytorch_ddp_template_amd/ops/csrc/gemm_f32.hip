@@ -189,7 +189,9 @@ __global__ __launch_bounds__(THREADS) void gemm_tn_f32_kernel(
       // B
       f32x4 vb = {};
       if (MODE == MODE_CONV) {
-        if (gm < Mtot) {
+        // Cin is pow2 >= 4 and sc0 % 4 == 0: a 4-group never straddles Cin,
+        // so guarding its first channel keeps the whole load inside the pixel
+        if (gm < Mtot && j0 + sc0 < J) {
           int t = gm;
           const int wo = t % cm.WO;
           t /= cm.WO;

@@ -241,3 +241,79 @@ def test_fused_bottleneck_matches_unfused():
         assert torch.allclose(xf.float(), x2.grad.float(), atol=3e-2, rtol=3e-2)
         for a, p in zip(gf, blk.parameters()):
             assert torch.allclose(a.float(), p.grad.float(), atol=5e-2, rtol=5e-2)
+
+
+# ---------------- fp32 (the command-line default dtype) vs the CPU path ----
+
+
+def _fwd_bwd_f32(model, x, y):
+    from pytorch_ddp_template_amd.ops import CrossEntropyLoss
+
+    model.zero_grad(set_to_none=True)
+    logits = model(x)
+    CrossEntropyLoss()(logits, y).backward()
+    out = {"logits": logits.detach().cpu()}
+    for n, p in model.named_parameters():
+        assert p.grad is not None, f"{n}: no gradient"
+        out[n] = p.grad.detach().cpu()
+    return out
+
+
+def _assert_f32_model_matches_cpu(make, x, y, tag):
+    """One fp32 forward+backward on the GPU vs the same model on the CPU
+    path: logits and every parameter gradient within 8x the CPU path's own
+    sensitivity to a +-1 ulp perturbation of the input (4 seeded draws,
+    largest change per tensor, normalised by max|tensor|)."""
+    torch.manual_seed(11)
+    m = make()
+    m.train()
+    mg = make()
+    mg.load_state_dict(m.state_dict())
+    mg.train()
+    mg = mg.to(DEV)
+    base = _fwd_bwd_f32(m, x, y)
+    noise = {k: 0.0 for k in base}
+    for seed in range(4):
+        g = torch.Generator().manual_seed(100 + seed)
+        up = torch.randint(0, 2, x.shape, generator=g).bool()
+        inf = torch.full_like(x, float("inf"))
+        xp = torch.nextafter(x, torch.where(up, inf, -inf))
+        pert = _fwd_bwd_f32(m, xp, y)
+        for k, t in base.items():
+            d = ((pert[k] - t).abs().max() / t.abs().max()).item()
+            noise[k] = max(noise[k], d)
+    got = _fwd_bwd_f32(mg, x.to(DEV), y.to(DEV))
+    bad = []
+    for k, t in base.items():
+        err = ((got[k] - t).abs().max() / t.abs().max()).item()
+        print(f"MODELF32 {tag} {k} err={err:.3e} noise={noise[k]:.3e} "
+              f"ratio={err / noise[k] if noise[k] else float('inf'):.2f}")
+        if not err <= 8 * noise[k]:
+            bad.append(f"{k}: err {err:.3e} > 8 * noise {noise[k]:.3e}")
+    assert not bad, f"{tag}: " + "; ".join(bad)
+
+
+def test_resnet18_f32_fwd_bwd_matches_cpu():
+    """fp32 switches the fused blocks off: every conv runs conv2d_fwd_f32,
+    the zero-stuff dgrad and conv2d_wgrad_f32, plus the fp32 BN / pool /
+    linear / CE instantiations."""
+    from pytorch_ddp_template_amd.models import resnet18
+
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(8, 32, 32, 3, generator=g)
+    y = torch.randint(0, 10, (8,), generator=g)
+    _assert_f32_model_matches_cpu(
+        lambda: resnet18(num_classes=10, stem="cifar"), x, y, "resnet18")
+
+
+def test_vit_tiny_f32_fwd_bwd_matches_cpu():
+    """In fp32 ViT attention is composed from the batched fp32 GEMMs and the
+    softmax kernel (the fused attention kernels are 16-bit only)."""
+    from pytorch_ddp_template_amd.models.vit import ViT
+
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(4, 32, 32, 3, generator=g)
+    y = torch.randint(0, 10, (4,), generator=g)
+    _assert_f32_model_matches_cpu(
+        lambda: ViT(image_size=32, patch_size=8, dim=64, depth=2, heads=4,
+                    num_classes=10), x, y, "vit_tiny")

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _errbound import poison
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -132,9 +134,7 @@ def _poison_allocator(numel):
     (The round-2 wide-N bug left half of C unwritten: first call ran on
     driver-zeroed pages and every loop iteration recycled the same block, so
     plain unit tests and short training loops both passed.)"""
-    junk = torch.full((numel,), float("nan"), dtype=torch.bfloat16, device=DEV)
-    del junk
-    torch.cuda.synchronize()
+    poison(DEV, 2 * numel)
 
 
 def conv_ref(x, w, stride, pad):
