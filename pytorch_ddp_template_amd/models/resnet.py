@@ -45,6 +45,10 @@ class BasicBlock(nn.Module):
     def __init__(self, in_ch, ch, stride=1):
         super().__init__()
         self.stride = stride
+        # ReLU-mask handshake with the neighbouring blocks (fused_block.py);
+        # off for a standalone block, ResNet wires consecutive blocks
+        self._out_to_block = False
+        self._in_from_block = False
         self.conv1 = _conv_bn(in_ch, ch, 3, stride, 1, act="relu")
         self.conv2 = _conv_bn(ch, ch, 3, 1, 1)
         self.down = (
@@ -75,6 +79,7 @@ class BasicBlock(nn.Module):
                 self.down[0] if self.down is not None else None,
                 self.down[1] if self.down is not None else None,
                 self.stride,
+                offer=self._out_to_block, accept=self._in_from_block,
             )
         idt = x if self.down is None else self.down(x)
         out = self.conv2(self.conv1(x))
@@ -87,6 +92,8 @@ class Bottleneck(nn.Module):
     def __init__(self, in_ch, ch, stride=1):
         super().__init__()
         self.stride = stride
+        self._out_to_block = False
+        self._in_from_block = False
         self.conv1 = _conv_bn(in_ch, ch, 1, 1, 0, act="relu")
         self.conv2 = _conv_bn(ch, ch, 3, stride, 1, act="relu")
         self.conv3 = _conv_bn(ch, ch * self.expansion, 1, 1, 0)
@@ -111,10 +118,22 @@ class Bottleneck(nn.Module):
                 self.down[0] if self.down is not None else None,
                 self.down[1] if self.down is not None else None,
                 self.stride,
+                offer=self._out_to_block, accept=self._in_from_block,
             )
         idt = x if self.down is None else self.down(x)
         out = self.conv3(self.conv2(self.conv1(x)))
         return add_relu(out, idt)
+
+
+def wire_blocks(blocks):
+    """Let consecutive residual blocks, each the SOLE consumer of its
+    predecessor's output, hand over a pre-masked gradient (fused_block.py:
+    the consumer's dgrad epilogue applies the producer's ReLU mask).  It only
+    permits the handshake; each forward call settles whether it happens."""
+    blocks = list(blocks)
+    for prod, cons in zip(blocks[:-1], blocks[1:]):
+        prod._out_to_block = True
+        cons._in_from_block = True
 
 
 class ResNet(nn.Module):
@@ -137,6 +156,12 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(block, 512, layers[3], 2)
         self.pool = GlobalAvgPoolNHWC()
         self.fc = Linear(512 * block.expansion, num_classes)
+        # consecutive blocks (across the layer boundaries too) hand over a
+        # pre-masked gradient.  The first block does not mask the stem
+        # output's grad (the stem's bn_bwd applies that ReLU mask itself);
+        # the last block keeps its relu_bwd (the average pool does not mask).
+        wire_blocks([b for layer in (self.layer1, self.layer2, self.layer3,
+                                     self.layer4) for b in layer])
 
     def _make_layer(self, block, ch, n, stride):
         blocks = [block(self.in_ch, ch, stride)]

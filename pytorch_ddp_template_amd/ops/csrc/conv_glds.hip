@@ -13,7 +13,8 @@
 // XOR k-slot swizzle, mfma_f32_16x16x32_bf16, XCD-bijective remap,
 // LDS-staged coalesced epilogue.  Optional BN-stats epilogue (partial
 // col sums/sumsq) matching the NT/halo workspace convention so the fused
-// conv+BN path (bn_fwd_ws) consumes it unchanged.
+// conv+BN path (bn_fwd_ws) consumes it unchanged.  Optional dgrad epilogue
+// (skip-grad addend and/or ReLU mask in the coalesced store phase, EPI_*).
 //
 // Eligibility (host): bf16, pow2 HO/WO, C % 64 == 0, M % BM == 0,
 // Kout % BN == 0.  Tiles: BN=256/128 at BM=256, BN=64 at BM=512 — always
@@ -51,12 +52,23 @@ struct Geom {
   int lgSt = 0;
 };
 
-template <int BM, int BN, bool STATS, int MINB = 1>
+// Store-phase epilogue modes (dgrad only; bit 0 = addend, bit 1 = mask):
+//   y = relu_bwd(bf16(float(bf16(acc)) + float(addend)), out_mask)
+// with each part optional.  Both operands are read in the coalesced store
+// layout (one 16-B chunk per lane per row), AFTER the accumulator has been
+// rounded to bf16 — bit-identical to the separate ew::AddOp / ew::ReluBwdOp
+// passes it replaces.
+constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_MASK = 2, EPI_ADD_MASK = 3;
+
+template <int BM, int BN, bool STATS, int MINB = 1, int EPI = EPI_NONE>
 __global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, const __hip_bfloat16* __restrict__ zpad,
     int M, int N /*Kout*/, int K /*RSC*/, Geom g,
-    float* __restrict__ stats_ws, int ws_nblocks) {
+    float* __restrict__ stats_ws, int ws_nblocks,
+    const __hip_bfloat16* __restrict__ addend,
+    const __hip_bfloat16* __restrict__ out_mask) {
+  static_assert(!(STATS && EPI != EPI_NONE), "dgrad epilogues carry no stats");
   __shared__ __hip_bfloat16 smem[2 * (BM + BN) * BK];
 
   const int tid = threadIdx.x;
@@ -225,6 +237,31 @@ __global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
 
   // ---- epilogue: stage the y tile through LDS for coalesced rows
   __hip_bfloat16* cs = smem;  // [BM][BN] bf16
+  constexpr int CPR = BN / 8;        // 16B chunks per row
+  constexpr int RPR = THREADS / CPR; // rows per round
+  constexpr int NR = BM / RPR;       // store rounds
+  const int wrow = tid / CPR, wchunk = tid % CPR;
+  // addend / mask chunks ride PF rounds ahead of the store that uses them:
+  // the first PF rounds are issued here, so their latency hides behind the
+  // LDS staging + barrier; the rest are issued one round at a time inside
+  // the store loop (never all NR rounds in registers at once).
+  constexpr bool HAS_ADD = (EPI & EPI_ADD) != 0;
+  constexpr bool HAS_MASK = (EPI & EPI_MASK) != 0;
+  constexpr int PF = 2;
+  static_assert(NR >= PF, "epilogue prefetch deeper than the store loop");
+  short8 av[PF] = {}, mv[PF] = {};
+  auto epi_load = [&](int r, int slot) {
+    const long long off =
+        ((m0 + r * RPR + wrow) * N + n0) * 2 + wchunk * 16;  // bytes
+    if constexpr (HAS_ADD)
+      av[slot] = *(const short8*)((const char*)addend + off);
+    if constexpr (HAS_MASK)
+      mv[slot] = *(const short8*)((const char*)out_mask + off);
+  };
+  if constexpr (EPI != EPI_NONE) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p) epi_load(p, p);
+  }
 #pragma unroll
   for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
@@ -237,14 +274,25 @@ __global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
       }
     }
   __syncthreads();
-  constexpr int CPR = BN / 8;        // 16B chunks per row
-  constexpr int RPR = THREADS / CPR; // rows per round
-  const int wrow = tid / CPR, wchunk = tid % CPR;
 #pragma unroll
-  for (int r = 0; r < BM / RPR; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const int row = r * RPR + wrow;
-    *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) =
-        *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
+    short8 c = *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
+    if constexpr (EPI != EPI_NONE) {
+      const short8 a = av[r % PF], m = mv[r % PF];
+      if (r + PF < NR) epi_load(r + PF, r % PF);
+      // same per-element op chain as ew::binary_kernel<bf16, AddOp> then
+      // <bf16, ReluBwdOp>: fp32 add, RNE to bf16, then 0 where !(mask > 0)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        short v = c[j];
+        if constexpr (HAS_ADD) v = f2bfbits(bfbits2f(v) + bfbits2f(a[j]));
+        if constexpr (HAS_MASK)
+          v = f2bfbits(bfbits2f(m[j]) > 0.f ? bfbits2f(v) : 0.f);
+        c[j] = v;
+      }
+    }
+    *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
   }
 }
 
@@ -252,10 +300,14 @@ __global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
 
 // Host entry: returns true when handled.  y must be pre-allocated
 // [N,HO,WO,Kout]; stats_ws (optional) pre-zeroed [2*ws_nblocks, Kout].
+// addend / out_mask (optional, dgrad only, never with stats_ws): y-shaped
+// contiguous tensors applied in the store phase — see cg::EPI_*.
 bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
                         torch::Tensor& y, const torch::Tensor& zp,
                         int64_t stride, int64_t pad, float* stats_ws,
-                        int ws_nblocks, int lgSt) {
+                        int ws_nblocks, int lgSt,
+                        const c10::optional<torch::Tensor>& addend,
+                        const c10::optional<torch::Tensor>& out_mask) {
   static const char* e = getenv("PDT_CONV_GLDS");
   if (e && e[0] == '0') return false;
   if (x.scalar_type() != torch::kBFloat16) return false;
@@ -289,16 +341,39 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
   const auto* wp = reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
   auto* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
   const auto* zpp = reinterpret_cast<const __hip_bfloat16*>(zp.data_ptr());
+  const int epi = (addend.has_value() ? cg::EPI_ADD : 0) |
+                  (out_mask.has_value() ? cg::EPI_MASK : 0);
+  const __hip_bfloat16 *addp = nullptr, *maskp = nullptr;
+  for (const auto* t : {&addend, &out_mask}) {
+    if (!t->has_value()) continue;
+    TORCH_CHECK(!stats_ws,
+                "conv glds: addend/out_mask exclude the stats epilogue");
+    TORCH_CHECK((*t)->is_cuda() && (*t)->is_contiguous() &&
+                    (*t)->scalar_type() == x.scalar_type() &&
+                    (*t)->numel() == y.numel(),
+                "conv glds: addend/out_mask must be contiguous, of dy's dtype "
+                "and dx-sized");
+  }
+  if (addend.has_value())
+    addp = reinterpret_cast<const __hip_bfloat16*>(addend->data_ptr());
+  if (out_mask.has_value())
+    maskp = reinterpret_cast<const __hip_bfloat16*>(out_mask->data_ptr());
+#define LAUNCH_CG_E(BMv, BNv, ST, MB, EP)                                    \
+  hipLaunchKernelGGL((cg::conv_fwd_glds_kernel<BMv, BNv, ST, MB, EP>), grid, \
+                     dim3(cg::THREADS), 0, stream, xp, wp, yp, zpp, (int)M,  \
+                     Kout, K, g, stats_ws, ws_nblocks, addp, maskp)
 #define LAUNCH_CG(BMv, BNv, MB)                                              \
   do {                                                                       \
     if (stats_ws)                                                            \
-      hipLaunchKernelGGL((cg::conv_fwd_glds_kernel<BMv, BNv, true, MB>),     \
-                         grid, dim3(cg::THREADS), 0, stream, xp, wp, yp,     \
-                         zpp, (int)M, Kout, K, g, stats_ws, ws_nblocks);     \
+      LAUNCH_CG_E(BMv, BNv, true, MB, cg::EPI_NONE);                         \
+    else if (epi == cg::EPI_NONE)                                            \
+      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_NONE);                        \
+    else if (epi == cg::EPI_ADD)                                             \
+      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_ADD);                         \
+    else if (epi == cg::EPI_MASK)                                            \
+      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_MASK);                        \
     else                                                                     \
-      hipLaunchKernelGGL((cg::conv_fwd_glds_kernel<BMv, BNv, false, MB>),    \
-                         grid, dim3(cg::THREADS), 0, stream, xp, wp, yp,     \
-                         zpp, (int)M, Kout, K, g, nullptr, 0);               \
+      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_ADD_MASK);                    \
   } while (0)
   // Kout=64: A/B between one 512x64 block/CU and two co-resident 256x64
   // blocks (80 KB LDS each — exactly 2/CU; better glds latency hiding)
@@ -314,6 +389,7 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
   else if (BM == 512) LAUNCH_CG(512, 64, 1);
   else LAUNCH_CG(256, 64, 2);
 #undef LAUNCH_CG
+#undef LAUNCH_CG_E
   return true;
 }
 
@@ -322,5 +398,5 @@ bool conv2d_fwd_glds(const torch::Tensor& x, const torch::Tensor& w,
                      int64_t stride, int64_t pad, float* stats_ws,
                      int ws_nblocks) {
   return conv2d_fwd_glds_ex(x, w, y, zp, stride, pad, stats_ws, ws_nblocks,
-                            0);
+                            0, c10::nullopt, c10::nullopt);
 }

@@ -1375,7 +1375,11 @@ bool conv2d_fwd_glds(const torch::Tensor& x, const torch::Tensor& w,
 bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
                         torch::Tensor& y, const torch::Tensor& zp,
                         int64_t stride, int64_t pad, float* stats_ws,
-                        int ws_nblocks, int lgSt);
+                        int ws_nblocks, int lgSt,
+                        const c10::optional<torch::Tensor>& addend,
+                        const c10::optional<torch::Tensor>& out_mask);
+// elementwise.hip
+torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y);
 
 // conv2d forward, NHWC x[N,H,W,C] * w[Kout,R,S,C] -> y[N,HO,WO,Kout]
 // stats=true additionally returns the BN partial workspace ws
@@ -1449,11 +1453,17 @@ std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
 // zero-stuffing folded into the im2col gather (ConvMeta.ss) — the stuffed
 // tensor is never materialized.  dy[N,HO,WO,Kout], wr[Cin,R,S,Kout] (the
 // 180°-rotated weight), stride/pad are the ORIGINAL forward conv's.
+// dx = relu_bwd(dgrad + (addend_mask > 0 ? addend : 0), out_mask), every
+// part optional.  On the glds route addend and out_mask ride in the
+// kernel's coalesced store phase (bit-identical to separate add_ / relu_bwd
+// passes); elsewhere the addend uses the NT kernel's EXTRAS epilogue and
+// out_mask a relu_bwd pass over the result.
 torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
                                 int64_t stride, int64_t pad, int64_t H,
                                 int64_t W,
                                 c10::optional<torch::Tensor> addend,
-                                c10::optional<torch::Tensor> addend_mask) {
+                                c10::optional<torch::Tensor> addend_mask,
+                                c10::optional<torch::Tensor> out_mask) {
   int N = (int)dy.size(0), HOs = (int)dy.size(1), WOs = (int)dy.size(2),
       Kout = (int)dy.size(3);
   int Cin = (int)wr.size(0), R = (int)wr.size(1), S = (int)wr.size(2);
@@ -1482,16 +1492,27 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
   // only on the stride grid, indexed by the un-stuffed position)
   static const char* e_gs2 = getenv("PDT_CONV_GLDS_S2");
   const bool glds_s2 = !(e_gs2 && e_gs2[0] == '0');
-  if (!addend.has_value() && ((int)stride & ((int)stride - 1)) == 0 &&
+  if (out_mask.has_value())
+    TORCH_CHECK(out_mask->is_contiguous() &&
+                out_mask->numel() == dx.numel() &&
+                out_mask->scalar_type() == dy.scalar_type(),
+                "dgrad: out_mask must be contiguous, dx-sized, of dy's dtype");
+  auto masked = [&](torch::Tensor t) {
+    return out_mask.has_value() ? relu_bwd(t, *out_mask) : t;
+  };
+  // a masked addend (addend_mask) is not an epilogue mode of the glds
+  // kernel: that combination keeps the NT route
+  const bool glds_epi_ok = !(addend.has_value() && addend_mask.has_value());
+  if (glds_epi_ok && ((int)stride & ((int)stride - 1)) == 0 &&
       ((int)stride == 1 || glds_s2)) {
     const int lgSt = log2_exact((int)stride);
-    if (lgSt >= 0 &&
-        conv2d_fwd_glds_ex(dy, wr, dx, zp, 1, dpad, nullptr, 0, lgSt))
+    if (lgSt >= 0 && conv2d_fwd_glds_ex(dy, wr, dx, zp, 1, dpad, nullptr, 0,
+                                        lgSt, addend, out_mask))
       return dx;
   }
   if ((int)stride == 1 && !addend.has_value() &&
       conv2d_fwd_halo(dy, wr, dx, zp, 1, dpad, nullptr, 0))
-    return dx;
+    return masked(dx);
   NtExtras ex{};
   if (addend.has_value()) {
     TORCH_CHECK(addend->is_contiguous() && addend->numel() == dx.numel() &&
@@ -1510,7 +1531,7 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
   else
     launch_nt16<_Float16, g16::MODE_CONV>(dy, wr, dx, {}, false, zp, grid, M,
                                           Cin, K, 0, 0, 0, cm, ex);
-  return dx;
+  return masked(dx);
 }
 
 // C[I,J] = A[...,M,I]^T @ B[...,M,J] summed over batch? No — per batch.

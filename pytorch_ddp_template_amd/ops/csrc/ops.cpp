@@ -49,7 +49,8 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
                                 int64_t stride, int64_t pad, int64_t H,
                                 int64_t W,
                                 c10::optional<torch::Tensor> addend,
-                                c10::optional<torch::Tensor> addend_mask);
+                                c10::optional<torch::Tensor> addend_mask,
+                                c10::optional<torch::Tensor> out_mask);
 std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
     torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
     int64_t stride, int64_t pad, bool relu);
@@ -219,9 +220,12 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
 torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
                            int64_t pad, int64_t H, int64_t W,
                            c10::optional<torch::Tensor> addend,
-                           c10::optional<torch::Tensor> addend_mask) {
+                           c10::optional<torch::Tensor> addend_mask,
+                           c10::optional<torch::Tensor> out_mask) {
   // dx = conv(zero_stuffed(dy), rot(w), stride=1, pad=R-1-pad); output
   // padding covers (H+2p-R) % stride != 0 (inputs the fwd never reached).
+  // Full contract: dx = relu_bwd(dgrad + masked(addend), out_mask), each
+  // part optional, whichever kernel runs.
   int R = (int)w.size(1), S = (int)w.size(2);
   TORCH_CHECK(pad <= R - 1 && pad <= S - 1, "dgrad needs pad <= kernel-1");
   auto wr = weight_rot(w.contiguous());  // [C, R, S, Kout]
@@ -230,7 +234,7 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
     // bf16/f16 fast path: zero-stuffing folded into the GEMM's im2col
     // gather (never materialized) — gemm_bf16.hip conv2d_dgrad_bf16.
     return conv2d_dgrad_bf16(dy.contiguous(), wr, stride, pad, H, W, addend,
-                             addend_mask);
+                             addend_mask, out_mask);
   }
   int64_t opad_h = (H + 2 * pad - R) % stride;
   int64_t opad_w = (W + 2 * pad - S) % stride;
@@ -243,6 +247,9 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
       a = a * (addend_mask->reshape(a.sizes()) > 0).to(a.scalar_type());
     dx = dx + a.reshape(dx.sizes());
   }
+  if (out_mask.has_value())
+    dx = torch::where(out_mask->reshape(dx.sizes()) > 0, dx,
+                      torch::zeros_like(dx));
   TORCH_CHECK(dx.size(1) == H && dx.size(2) == W,
               "dgrad shape mismatch: got ", dx.sizes(), " want H=", H, " W=",
               W, " (input H+2p-R must be divisible by stride)");
@@ -294,7 +301,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_dgrad", &conv2d_dgrad, py::arg("dy"), py::arg("w"),
         py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"),
         py::arg("addend") = c10::nullopt,
-        py::arg("addend_mask") = c10::nullopt);
+        py::arg("addend_mask") = c10::nullopt,
+        py::arg("out_mask") = c10::nullopt);
   m.def("conv2d_fwd_stats", &conv2d_fwd_stats_bf16, py::arg("x"),
         py::arg("w"), py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
         py::arg("pad") = 0, py::arg("relu") = false);

@@ -8,11 +8,30 @@ Why (measured on MI355X, ResNet-18/CIFAR bf16 step profile):
 * BN backward applies the downstream ReLU mask inline (``bn_bwd(y_relu=·)``)
   — no relu_bwd pass;
 * the residual add + final ReLU ride in the last BN's normalize epilogue
-  (``bn_fwd_ws(addend=·)``) — the separate add_relu pass disappears.
-  (The backward-side equivalent — accumulating the skip grad inside the
-  conv dgrad epilogue — was measured SLOWER (+200 us/launch of per-lane
-  2-B gathers against the MFMA C-layout scatter) and reverted; the skip
-  grad uses a plain bandwidth-bound add.)
+  (``bn_fwd_ws(addend=·)``) — the separate add_relu pass disappears;
+* the backward-side equivalent: the skip-grad accumulation and the
+  block-input ReLU mask ride in the store phase of the block's last dgrad
+  (``conv2d_dgrad(addend=·, out_mask=·)``) — the separate ``add_`` pass and
+  the next-upstream block's ``relu_bwd`` pass disappear.  An earlier attempt
+  at the add lost (+200 us/launch) because the kernel of that time, the NT
+  GEMM, had to gather the addend per lane in 2-B pieces in the MFMA C/D
+  layout.  The dgrads now run on the glds conv kernel, whose epilogue
+  already stages the tile through LDS and stores coalesced 16-B row chunks;
+  addend and mask are read with that same pattern, after the accumulator is
+  rounded to bf16, so the result is bit-identical to the separate passes.
+
+ReLU-mask handshake between adjacent blocks (``PDT_DGRAD_EPILOGUE``, below):
+a block's output is ``relu(·)``, and its backward starts by masking ``dy``
+with ``out > 0``.  When the block downstream consumed exactly that output
+through this fused path, it applies the mask itself (its ``x`` IS this
+``out``) in its dgrad epilogue, and this block skips its ``relu_bwd``.  The
+agreement is made per forward call on the producer's autograd node
+(``dy_premasked``): the producer offers it only when ``ResNet`` wired it to a
+following block, the consumer accepts only when its input's ``grad_fn`` is
+such an offering node.  A consumer on the unfused module path never accepts,
+so its producer masks as before; a standalone block neither offers nor
+accepts.  The wiring assumes the producer's output has no other consumer
+(true for the ``nn.Sequential`` layers of ``models/resnet.py``).
 
 The unfused module path (ops/modules.py) remains the CPU/eval/odd-shape
 reference; tests compare the two.  Reference scope note: the reference
@@ -46,6 +65,35 @@ def _use_streams():
     return os.environ.get("PDT_FUSED_STREAMS", "0") == "1"
 
 
+def _use_dgrad_epilogue():
+    # skip-grad add + input ReLU mask inside the dgrad store phase;
+    # PDT_DGRAD_EPILOGUE=0 restores the separate add_ / relu_bwd passes
+    # (A/B runs).  Read once per block forward; the backward follows it.
+    return os.environ.get("PDT_DGRAD_EPILOGUE", "1") != "0"
+
+
+def _accept_premask(x, accept, epi):
+    """Consumer side of the handshake: True when this block will mask its
+    returned dx by ``x > 0`` and has told x's producer so."""
+    if not (accept and epi):
+        return False
+    fn = x.grad_fn
+    if getattr(fn, "dy_premasked", None) is None:
+        return False
+    fn.dy_premasked = True
+    return True
+
+
+def _skip_grad_dgrad(ext, ctx, dyc, w, stride, pad, H, W, addend, x):
+    """dx = dgrad(dyc, w) + addend, masked by x > 0 when this block agreed to
+    (ctx.mask_in); fused into the dgrad epilogue unless gated off."""
+    if ctx.epi:
+        return ext.conv2d_dgrad(dyc, w, stride, pad, H, W, addend=addend,
+                                out_mask=x if ctx.mask_in else None)
+    # in-place in-house add (the skip grad rides the dgrad output buffer)
+    return ext.add_(ext.conv2d_dgrad(dyc, w, stride, pad, H, W), addend)
+
+
 def _flat(t):
     return t.reshape(-1, t.shape[-1])
 
@@ -53,9 +101,13 @@ def _flat(t):
 class _FusedBasicBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(
-        ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, bn1, bn2, bnd, stride
+        ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, bn1, bn2, bnd, stride,
+        offer=False, mask_in=False, epi=False,
     ):
         ext = native()
+        # handshake state (module docstring): None = no offer made
+        ctx.epi, ctx.mask_in = epi, mask_in
+        ctx.dy_premasked = False if (offer and epi) else None
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
         t1, ws1 = ext.conv2d_fwd_stats(x, w1, None, stride, 1, False)
@@ -100,8 +152,9 @@ class _FusedBasicBlockFn(torch.autograd.Function):
         Hz, Wz = z.shape[1], z.shape[2]
 
         # apply the add_relu mask ONCE; bn2/bnd backwards then read two
-        # tensors instead of three, and the skip grad is g itself
-        g = ext.relu_bwd(dy, out)
+        # tensors instead of three, and the skip grad is g itself.  When the
+        # downstream block already masked dy in its dgrad epilogue, dy is g.
+        g = dy if ctx.dy_premasked else ext.relu_bwd(dy, out)
         g2d = _flat(g)
         dx2, dg2, db2 = ext.bn_bwd(g2d, _flat(t2), g2, mean2, rstd2, None)
         dx2 = dx2.reshape(t2.shape)
@@ -129,9 +182,7 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             dw1 = ext.conv2d_wgrad(dt1, x, stride, 1, 3, 3).to(w1.dtype)
 
         if wd is None:
-            # in-place in-house add (the skip grad rides the dgrad output
-            # buffer; round 1 used an eager out-of-place torch add here)
-            dx = ext.add_(ext.conv2d_dgrad(dt1, w1, stride, 1, H, W), g)
+            dx = _skip_grad_dgrad(ext, ctx, dt1, w1, stride, 1, H, W, g, x)
             dwd = dgd = dbd = None
         else:
             dxa = ext.conv2d_dgrad(dt1, w1, stride, 1, H, W)
@@ -143,7 +194,7 @@ class _FusedBasicBlockFn(torch.autograd.Function):
                     dwd = ext.conv2d_wgrad(dtd, x, stride, 0, 1, 1).to(wd.dtype)
             else:
                 dwd = ext.conv2d_wgrad(dtd, x, stride, 0, 1, 1).to(wd.dtype)
-            dx = ext.add_(ext.conv2d_dgrad(dtd, wd, stride, 0, H, W), dxa)
+            dx = _skip_grad_dgrad(ext, ctx, dtd, wd, stride, 0, H, W, dxa, x)
         if use_side:
             # weight grads are consumed (bucket accumulation) on the main
             # stream after this node returns
@@ -151,18 +202,24 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             for t in (dw2, dw1) + ((dwd,) if wd is not None else ()):
                 t.record_stream(main)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd,
-                None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
-def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride):
-    """Run a BasicBlock through the fused Function (training, native path)."""
+def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride,
+                      offer=False, accept=False):
+    """Run a BasicBlock through the fused Function (training, native path).
+
+    offer / accept: this block's output feeds / its input comes from an
+    adjacent wired block (ReLU-mask handshake, module docstring)."""
+    epi = _use_dgrad_epilogue()
+    mask_in = _accept_premask(x, accept, epi)
     return _FusedBasicBlockFn.apply(
         x, conv1.weight, bn1.weight, bn1.bias,
         conv2.weight, bn2.weight, bn2.bias,
         convd.weight if convd is not None else None,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
-        bn1, bn2, bnd, stride,
+        bn1, bn2, bnd, stride, offer, mask_in, epi,
     )
 
 
@@ -172,8 +229,11 @@ class _FusedBottleneckFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd,
-                bn1, bn2, bn3, bnd, stride):
+                bn1, bn2, bn3, bnd, stride,
+                offer=False, mask_in=False, epi=False):
         ext = native()
+        ctx.epi, ctx.mask_in = epi, mask_in
+        ctx.dy_premasked = False if (offer and epi) else None
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
         t1, ws1 = ext.conv2d_fwd_stats(x, w1, None, 1, 0, False)
@@ -219,7 +279,7 @@ class _FusedBottleneckFn(torch.autograd.Function):
         H1, W1 = z1.shape[1], z1.shape[2]
         H2, W2 = z2.shape[1], z2.shape[2]
 
-        g = ext.relu_bwd(dy, out)
+        g = dy if ctx.dy_premasked else ext.relu_bwd(dy, out)
         g2d = _flat(g)
         dx3, dg3, db3 = ext.bn_bwd(g2d, _flat(t3), g3, mean3, rstd3, None)
         dx3 = dx3.reshape(t3.shape)
@@ -238,20 +298,23 @@ class _FusedBottleneckFn(torch.autograd.Function):
         dw1 = ext.conv2d_wgrad(dt1, x, 1, 0, 1, 1).to(w1.dtype)
 
         if wd is None:
-            dx = ext.add_(ext.conv2d_dgrad(dt1, w1, 1, 0, H, W), g)
+            dx = _skip_grad_dgrad(ext, ctx, dt1, w1, 1, 0, H, W, g, x)
             dwd = dgd = dbd = None
         else:
             dxa = ext.conv2d_dgrad(dt1, w1, 1, 0, H, W)
             dtd, dgd, dbd = ext.bn_bwd(g2d, _flat(td), gd, meand, rstdd, None)
             dtd = dtd.reshape(td.shape)
             dwd = ext.conv2d_wgrad(dtd, x, stride, 0, 1, 1).to(wd.dtype)
-            dx = ext.add_(ext.conv2d_dgrad(dtd, wd, stride, 0, H, W), dxa)
+            dx = _skip_grad_dgrad(ext, ctx, dtd, wd, stride, 0, H, W, dxa, x)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3,
-                dwd, dgd, dbd, None, None, None, None, None)
+                dwd, dgd, dbd, None, None, None, None, None,
+                None, None, None)
 
 
 def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
-                     stride):
+                     stride, offer=False, accept=False):
+    epi = _use_dgrad_epilogue()
+    mask_in = _accept_premask(x, accept, epi)
     return _FusedBottleneckFn.apply(
         x, conv1.weight, bn1.weight, bn1.bias,
         conv2.weight, bn2.weight, bn2.bias,
@@ -259,5 +322,5 @@ def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
         convd.weight if convd is not None else None,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
-        bn1, bn2, bn3, bnd, stride,
+        bn1, bn2, bn3, bnd, stride, offer, mask_in, epi,
     )
