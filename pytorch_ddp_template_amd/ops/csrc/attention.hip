@@ -1119,21 +1119,13 @@ torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor dout,
   return dqkv;
 }
 
-namespace {
-int attn_log2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return ((1 << l) == v) ? l : -1;
-}
-}  // namespace
-
 // qkv [N, S, 3*h*dh] -> (q, k, v) each [N*h, S, dh]
 std::vector<torch::Tensor> qkv_unpack(torch::Tensor qkv, int64_t heads) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous());
   const int N = (int)qkv.size(0), S = (int)qkv.size(1);
   const int h = (int)heads;
   const int dh = (int)(qkv.size(2) / (3 * h));
-  const int lg = attn_log2_exact(dh / 8);
+  const int lg = log2_exact(dh / 8);
   TORCH_CHECK(dh % 8 == 0 && lg >= 0, "qkv_unpack needs pow2 dh/8");
   auto opt = qkv.options();
   auto q = torch::empty({(long long)N * h, S, dh}, opt);
@@ -1165,7 +1157,7 @@ torch::Tensor qkv_pack(torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
               dq.scalar_type() == dv.scalar_type());
   const int h = (int)heads;
   const int S = (int)dq.size(1), dh = (int)dq.size(2);
-  const int lg = attn_log2_exact(dh / 8);
+  const int lg = log2_exact(dh / 8);
   TORCH_CHECK(dh % 8 == 0 && lg >= 0, "qkv_pack needs pow2 dh/8");
   auto dqkv = torch::empty({N, S, (long long)3 * h * dh}, dq.options());
   TORCH_CHECK(N <= 65535 && S <= 65535, "qkv_pack grid limits");
@@ -1199,7 +1191,7 @@ torch::Tensor head_split(torch::Tensor x, int64_t heads) {
   const int N = (int)x.size(0), S = (int)x.size(1);
   const int h = (int)heads;
   const int dh = (int)(x.size(2) / h);
-  const int lg = attn_log2_exact(dh / 8);
+  const int lg = log2_exact(dh / 8);
   TORCH_CHECK(dh % 8 == 0 && lg >= 0, "head_split needs pow2 dh/8");
   auto y = torch::empty({(long long)N * h, S, dh}, x.options());
   TORCH_CHECK((long long)N * h <= 65535, "head_split grid.z limit");

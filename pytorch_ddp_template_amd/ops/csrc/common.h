@@ -81,6 +81,13 @@ DEV_INLINE float block_reduce_sum(float v, float* lds_scratch /*BLOCK/64*/) {
   return total;
 }
 
+// log2 of a power of two; -1 for anything else (host)
+static inline int log2_exact(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return ((1 << l) == v) ? l : -1;
+}
+
 static inline int grid_1d(long long n, int block, int cap = 2048) {
   long long g = (n + block - 1) / block;
   if (g > cap) g = cap;

@@ -16,9 +16,10 @@
 // conv+BN path (bn_fwd_ws) consumes it unchanged.  Optional dgrad epilogue
 // (skip-grad addend and/or ReLU mask in the coalesced store phase, EPI_*).
 //
-// Eligibility (host): bf16, pow2 HO/WO, C % 64 == 0, M % BM == 0,
-// Kout % BN == 0.  Tiles: BN=256/128 at BM=256, BN=64 at BM=512 — always
-// 8 waves, per-wave 128 M-rows (MI=8), NI = BN/64 capped at 4.
+// Eligibility (host): bf16, pow2 C >= 64, M % 256 == 0, Kout % 64 == 0.
+// Tiles: BM=256 by BN=256/128/64 (by Kout) — always 8 waves as 2(M)x4(N),
+// per-wave 128 M-rows (MI=8), NI = BN/64.  BN=64 tiles are 80 KB of LDS and
+// run two blocks per CU (better glds latency hiding).
 // Covers every non-stem ResNet-18/CIFAR conv (fwd and, via the rotated-
 // weight identity, stride-1 dgrad).  Reference scope: SURVEY §2b conv row.
 
@@ -32,7 +33,7 @@ namespace cg {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BK = 64;
+constexpr int BM = 256, BK = 64;
 constexpr int THREADS = 512;
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -60,8 +61,9 @@ struct Geom {
 // passes it replaces.
 constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_MASK = 2, EPI_ADD_MASK = 3;
 
-template <int BM, int BN, bool STATS, int MINB = 1, int EPI = EPI_NONE>
-__global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
+template <int BN, bool STATS, int EPI = EPI_NONE>
+__global__ __launch_bounds__(THREADS, BN == 64 ? 2 : 1)
+void conv_fwd_glds_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, const __hip_bfloat16* __restrict__ zpad,
     int M, int N /*Kout*/, int K /*RSC*/, Geom g,
@@ -153,9 +155,9 @@ __global__ __launch_bounds__(THREADS, MINB) void conv_fwd_glds_kernel(
   };
 
   // wave grid: always 128 M-rows per wave (MI=8)
-  constexpr int NWM = BM / 128;          // waves along M (2 or 4)
+  constexpr int NWM = BM / 128;          // waves along M
   constexpr int NWN = 8 / NWM;           // waves along N
-  constexpr int NI = BN / (16 * NWN);    // 16-col frags per wave (4 or 2)
+  constexpr int NI = BN / (16 * NWN);    // 16-col frags per wave (4, 2 or 1)
   const int wm = (wave / NWN) * 128;
   const int wn = (wave % NWN) * (NI * 16);
   const int frow = lane & 15;
@@ -316,34 +318,18 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
   const int Kout = (int)w.size(0), R = (int)w.size(1), S = (int)w.size(2);
   if (C < 64 || (C & (C - 1))) return false;
   const int HO = (int)y.size(1), WO = (int)y.size(2);
-  auto pow2l = [](int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return ((1 << l) == v) ? l : -1;
-  };
-  const int lgC = pow2l(C);
+  const int lgC = log2_exact(C);
   const long long M = (long long)N_ * HO * WO;
   const int K = R * S * C;
-  static const char* e_bn = getenv("PDT_CG_BN");
-  int BN = Kout % 256 == 0 ? 256 : Kout % 128 == 0 ? 128 : 64;
-  if (e_bn && e_bn[0] == '6') BN = 64;  // force the 2-block 64-wide route
   if (Kout % 64) return false;
-  int BM = BN == 64 ? 512 : 256;
-  if (M % BM) {
-    if (BM == 512 && M % 256 == 0) { BM = 256; BN = 64; }
-    else return false;
-  }
-  if (M / BM > 2147483647LL / 8) return false;
+  const int BN = Kout % 256 == 0 ? 256 : Kout % 128 == 0 ? 128 : 64;
+  if (M % cg::BM) return false;
+  if (M / cg::BM > 2147483647LL / 8) return false;
   cg::Geom g{H, W, C, lgC, HO, WO, (int)stride, (int)pad, S, R * S, lgSt};
   auto stream = c10::hip::getCurrentHIPStream();
-  dim3 grid(Kout / BN, (unsigned)(M / BM));
-  const auto* xp = reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  const auto* wp = reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  auto* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
-  const auto* zpp = reinterpret_cast<const __hip_bfloat16*>(zp.data_ptr());
+  dim3 grid(Kout / BN, (unsigned)(M / cg::BM));
   const int epi = (addend.has_value() ? cg::EPI_ADD : 0) |
                   (out_mask.has_value() ? cg::EPI_MASK : 0);
-  const __hip_bfloat16 *addp = nullptr, *maskp = nullptr;
   for (const auto* t : {&addend, &out_mask}) {
     if (!t->has_value()) continue;
     TORCH_CHECK(!stats_ws,
@@ -354,42 +340,21 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
                 "conv glds: addend/out_mask must be contiguous, of dy's dtype "
                 "and dx-sized");
   }
-  if (addend.has_value())
-    addp = reinterpret_cast<const __hip_bfloat16*>(addend->data_ptr());
-  if (out_mask.has_value())
-    maskp = reinterpret_cast<const __hip_bfloat16*>(out_mask->data_ptr());
-#define LAUNCH_CG_E(BMv, BNv, ST, MB, EP)                                    \
-  hipLaunchKernelGGL((cg::conv_fwd_glds_kernel<BMv, BNv, ST, MB, EP>), grid, \
-                     dim3(cg::THREADS), 0, stream, xp, wp, yp, zpp, (int)M,  \
-                     Kout, K, g, stats_ws, ws_nblocks, addp, maskp)
-#define LAUNCH_CG(BMv, BNv, MB)                                              \
-  do {                                                                       \
-    if (stats_ws)                                                            \
-      LAUNCH_CG_E(BMv, BNv, true, MB, cg::EPI_NONE);                         \
-    else if (epi == cg::EPI_NONE)                                            \
-      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_NONE);                        \
-    else if (epi == cg::EPI_ADD)                                             \
-      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_ADD);                         \
-    else if (epi == cg::EPI_MASK)                                            \
-      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_MASK);                        \
-    else                                                                     \
-      LAUNCH_CG_E(BMv, BNv, false, MB, cg::EPI_ADD_MASK);                    \
-  } while (0)
-  // Kout=64: A/B between one 512x64 block/CU and two co-resident 256x64
-  // blocks (80 KB LDS each — exactly 2/CU; better glds latency hiding)
-  static const char* e_l1 = getenv("PDT_CG_N64");
-  const bool n64_2b = !(e_l1 && e_l1[0] == '5');  // "5" -> 512x64 route
-  if (BN == 64 && n64_2b && M % 256 == 0) {
-    dim3 grid64(Kout / 64, (unsigned)(M / 256));
-    grid = grid64;
-    BM = 256;
-  }
-  if (BN == 256) LAUNCH_CG(256, 256, 1);
-  else if (BN == 128) LAUNCH_CG(256, 128, 1);
-  else if (BM == 512) LAUNCH_CG(512, 64, 1);
-  else LAUNCH_CG(256, 64, 2);
-#undef LAUNCH_CG
-#undef LAUNCH_CG_E
+  const bf16* addp = addend.has_value() ? ptr16<bf16>(*addend) : nullptr;
+  const bf16* maskp = out_mask.has_value() ? ptr16<bf16>(*out_mask) : nullptr;
+#define CG_KERN(ST, EP)                                       \
+  (BN == 256   ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
+   : BN == 128 ? &cg::conv_fwd_glds_kernel<128, ST, EP>       \
+               : &cg::conv_fwd_glds_kernel<64, ST, EP>)
+  auto kern = stats_ws                ? CG_KERN(true, cg::EPI_NONE)
+              : epi == cg::EPI_NONE   ? CG_KERN(false, cg::EPI_NONE)
+              : epi == cg::EPI_ADD    ? CG_KERN(false, cg::EPI_ADD)
+              : epi == cg::EPI_MASK   ? CG_KERN(false, cg::EPI_MASK)
+                                      : CG_KERN(false, cg::EPI_ADD_MASK);
+#undef CG_KERN
+  hipLaunchKernelGGL(kern, grid, dim3(cg::THREADS), 0, stream, ptr16<bf16>(x),
+                     ptr16<bf16>(w), ptr16<bf16>(y), ptr16<bf16>(zp), (int)M,
+                     Kout, K, g, stats_ws, ws_nblocks, addp, maskp);
   return true;
 }
 

@@ -27,6 +27,19 @@
     }                                                               \
   }()
 
+// Host launchers of the 16-bit GEMM / conv kernels: typed data pointer, and
+// a call of f with a bf16 or _Float16 tag value chosen by the tensor's dtype.
+template <typename T>
+inline T* ptr16(const torch::Tensor& t) {
+  return reinterpret_cast<T*>(t.data_ptr());
+}
+
+template <typename F>
+inline auto dispatch16(const torch::Tensor& t, F&& f) {
+  if (t.scalar_type() == torch::kBFloat16) return f(bf16{});
+  return f(_Float16{});
+}
+
 // float <-> T conversions used by generic kernels
 template <typename T>
 DEV_INLINE float to_f(T v);

@@ -95,7 +95,7 @@ enum { MODE_PLAIN = 0, MODE_CONV = 1, MODE_CONVJ = 2 };
 // EXTRAS=false compiles the epilogue extras out entirely (they cost
 // registers/codegen even when the pointers are null).
 template <typename T16, int MODE, bool RELU, bool HAS_BIAS, int BNT = BN,
-          bool EXTRAS = false, int NBUF = 3>
+          bool EXTRAS = false>
 __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
     const T16* __restrict__ A, const T16* __restrict__ B,
     T16* __restrict__ C, const T16* __restrict__ bias,
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
   // with glds in flight emits vmcnt(0) and drains the NEXT k-step's loads,
   // collapsing the pipeline (guide §6: -16..20%% at GEMM scale).  With 3
   // buffers each barrier only waits for loads issued TWO steps back.
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF_BYTES];
+  __shared__ __attribute__((aligned(16))) char smem[3 * BUF_BYTES];
 
   // ----- block swizzle (bijective XCD remap over the x*y grid) -----
   int nwg = gridDim.x * gridDim.y;
@@ -247,20 +247,12 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
   } while (0)
 
   stage(0, 0);
-  if (NBUF >= 3) {
-    if (KT > 1) stage(1, 1);
-    if (KT > 1) NT_WAIT_STAGE(); else NT_WAIT_ALL();
-  } else {
-    NT_WAIT_ALL();
-  }
+  if (KT > 1) stage(1, 1);
+  if (KT > 1) NT_WAIT_STAGE(); else NT_WAIT_ALL();
   asm volatile("s_barrier" ::: "memory");
   for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt % NBUF;
-    if (NBUF >= 3) {
-      if (kt + 2 < KT) stage((kt + 2) % NBUF, kt + 2);
-    } else {
-      if (kt + 1 < KT) stage((kt + 1) & 1, kt + 1);
-    }
+    const int buf = kt % 3;
+    if (kt + 2 < KT) stage((kt + 2) % 3, kt + 2);
     const char* baseA = &smem[buf * BUF_BYTES];
     const char* baseB = baseA + TILE_BYTES;
     using vec16 = typename M16<T16>::vec;
@@ -287,7 +279,7 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
           acc[mi][ni] = M16<T16>::mma32(af[mi], bf[ni], acc[mi][ni]);
     }
     if (kt + 1 < KT) {
-      if (NBUF >= 3 && kt + 2 < KT) NT_WAIT_STAGE(); else NT_WAIT_ALL();
+      if (kt + 2 < KT) NT_WAIT_STAGE(); else NT_WAIT_ALL();
       asm volatile("s_barrier" ::: "memory");
     }
   }
@@ -371,163 +363,6 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
   }
 }
 
-// ---------------------------------------------------------------- TN -----
-// C[I,J] (+)= sum_m A[m,I] * B[m,J], fp32 accumulation into global memory
-// via atomics (grid.z splits the M range).  Used for dW = dY^T X.
-// Staging transposes [m][i] chunks into padded LDS images [i][m] via
-// register staging + lane-paired b32 writes (glds cannot transpose).
-//
-// MODE_CONV gathers the B operand (im2col of x) on the fly for conv wgrad;
-// the j-tile then lives inside one (r,s) slice: j = c0_tile + c.
-template <typename T16, int MODE>
-__global__ __launch_bounds__(THREADS) void gemm_tn_bf16_kernel(
-    const T16* __restrict__ A, const T16* __restrict__ B,
-    float* __restrict__ C, int Mtot, int I, int J, int r, int s,
-    long long ldc, long long coff, ConvMeta cm) {
-  // C element (i, j) lives at C[coff + i*ldc + j] — conv wgrad writes a
-  // (r,s) slice of dw[Kout][R*S*C], so ldc != J there.
-  constexpr int BI = 64, BJ = 64, BMC = 32;  // m-chunk
-  // padded LDS row: +8 keeps 16-B alignment for the b128 fragment reads
-  // (row stride 80 B) while staying bank-conflict-free (banks r*20 mod 64
-  // are distinct over any 16 consecutive rows).
-  constexpr int ROW = BMC + 8;
-  using vec16 = typename M16<T16>::vec;
-  __shared__ __attribute__((aligned(16))) T16 lds[2 * BI * ROW];
-  T16* ldsA = lds;
-  T16* ldsB = lds + BI * ROW;
-
-  const int i0 = blockIdx.y * BI;
-  const int j0 = blockIdx.x * BJ;
-
-  // split-M: this block handles chunk range [c0, c1)
-  const int n_chunks = (Mtot + BMC - 1) / BMC;
-  const int per_z = (n_chunks + gridDim.z - 1) / gridDim.z;
-  const int ch0 = blockIdx.z * per_z;
-  const int ch1 = min(n_chunks, ch0 + per_z);
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-
-  // staging geometry: [32 m][64 cols] bf16 = 32 rows x 128 B; 256 lanes x
-  // 16 B covers it in one pass: lane -> m = tid>>3, col0 = (tid&7)*8.
-  const int sm = threadIdx.x >> 3;        // m row in chunk (0..31)
-  const int sc0 = (threadIdx.x & 7) * 8;  // first col of this 16B piece
-
-  f32x4 acc[2][2] = {};
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-  const int fr = lane & 15;
-  const int fs = lane >> 4;
-
-  for (int ch = ch0; ch < ch1; ++ch) {
-    const int mbase = ch * BMC;
-    const int gm = mbase + sm;
-    // ---- load + transpose-stage A chunk ([m][I] -> image [i][m]) ----
-    {
-      vec16 v = {};
-      if (gm < Mtot && i0 + sc0 < I) {
-        const long long off = (long long)gm * I + i0 + sc0;
-        if (off + 8 <= (long long)Mtot * I) {
-          v = *reinterpret_cast<const vec16*>(A + off);
-        } else {  // last-row partial chunk: element-wise guarded load
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (off + j < (long long)Mtot * I) v[j] = A[off + j];
-        }
-      }
-      // pair lanes (sm even/odd) to write b32 [i][m..m+1]
-      short8 mine = *reinterpret_cast<short8*>(&v);
-      short8 other;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) other[j] = __shfl_xor((int)mine[j], 8);
-      if (((threadIdx.x >> 3) & 1) == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned int pack = ((unsigned short)mine[j]) |
-                              (((unsigned int)(unsigned short)other[j]) << 16);
-          *reinterpret_cast<unsigned int*>(&ldsA[(sc0 + j) * ROW + sm]) = pack;
-        }
-      }
-    }
-    // ---- load + transpose-stage B chunk ----
-    {
-      vec16 v = {};
-      if (MODE == MODE_CONV) {
-        if (gm < Mtot) {
-          int t = gm;
-          const int wo = t % cm.WO;
-          t /= cm.WO;
-          const int ho = t % cm.HO;
-          const int n = t / cm.HO;
-          const int hi = ho * cm.stride - cm.pad + r;
-          const int wi = wo * cm.stride - cm.pad + s;
-          const int c = j0 + sc0;
-          if (hi >= 0 && hi < cm.H && wi >= 0 && wi < cm.W &&
-              c < (1 << cm.C_log2))
-            v = *reinterpret_cast<const vec16*>(
-                B + (((long long)n * cm.H + hi) * cm.W + wi) *
-                        (1LL << cm.C_log2) +
-                c);
-        }
-      } else {
-        if (gm < Mtot && j0 + sc0 < J) {
-          const long long off = (long long)gm * J + j0 + sc0;
-          if (off + 8 <= (long long)Mtot * J) {
-            v = *reinterpret_cast<const vec16*>(B + off);
-          } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (off + j < (long long)Mtot * J) v[j] = B[off + j];
-          }
-        }
-      }
-      short8 mine = *reinterpret_cast<short8*>(&v);
-      short8 other;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) other[j] = __shfl_xor((int)mine[j], 8);
-      if (((threadIdx.x >> 3) & 1) == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned int pack = ((unsigned short)mine[j]) |
-                              (((unsigned int)(unsigned short)other[j]) << 16);
-          *reinterpret_cast<unsigned int*>(&ldsB[(sc0 + j) * ROW + sm]) = pack;
-        }
-      }
-    }
-    __syncthreads();
-    // ---- MFMA: k dimension = m (BMC=32 -> one 16x16x32 per frag) ----
-    vec16 af[2], bfr[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      af[i] = *reinterpret_cast<const vec16*>(
-          &ldsA[(wm + i * 16 + fr) * ROW + fs * 8]);
-      bfr[i] = *reinterpret_cast<const vec16*>(
-          &ldsB[(wn + i * 16 + fr) * ROW + fs * 8]);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni] = M16<T16>::mma(af[mi], bfr[ni], acc[mi][ni]);
-    __syncthreads();
-  }
-
-  // ---- accumulate into C (f32) ----
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int col = j0 + wn + ni * 16 + fr;
-    if (col >= J) continue;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int row = i0 + wm + mi * 16 + fs * 4 + rr;
-        if (row >= I) continue;
-        atomicAdd(&C[coff + (long long)row * ldc + col], acc[mi][ni][rr]);
-      }
-    }
-  }
-}
-
 // ------------------------------------------------- TN conv wgrad (tr) ----
 // dw accumulation, all R*S taps fused in ONE launch, built on two gfx950
 // hardware paths instead of VALU shuffle-transposes:
@@ -561,21 +396,13 @@ __global__ __launch_bounds__(THREADS) void gemm_tn_bf16_kernel(
 // TI/TJ: MFMA fragments along I/J for the whole BLOCK tile — 2 gives 64x64
 // (the conv wgrad default; TAPS=9 already fills the accumulators), 4 gives
 // 128x128 (TAPS=1 large plain GEMMs, e.g. ViT linear weight grads, where
-// 64x64 tiles were instruction-bound at 4 MFMAs per staged chunk), 8 with
-// WI=2/WJ=4 gives 256x256 on 8 waves (512 threads) — the r2 route for the
-// big ViT shapes: at 128x128 each operand is re-read ~6x from HBM and the
-// kernel sits on that traffic roofline (~450-510 TF measured, and rocBLAS
-// lands in the same band); 256x256 halves the re-reads.
+// 64x64 tiles were instruction-bound at 4 MFMAs per staged chunk).
 // WI/WJ: the wave grid (WI*WJ waves per block) splitting the block tile.
-// NBUF: LDS staging depth.  3 enables counted vmcnt waits (stage chunk n+2
-// while chunk n computes; the barrier only waits for loads issued one chunk
-// back) — essential at 1 workgroup/CU where __syncthreads()'s vmcnt(0)
-// would drain the just-prefetched chunk and expose full HBM latency every
-// 32 m-rows.  2 keeps the original drain-at-barrier behavior (fine for the
-// conv variants where 2 co-resident WGs hide each other's stalls).
+// LDS staging is double-buffered and drains at the barrier: 2 co-resident
+// workgroups hide each other's stalls.
 template <typename T16, int TAPS, int MODE = MODE_CONV, int TI = 2,
-          int TJ = 2, int WI = 2, int WJ = 2, int NBUF = 2, int FUSE = 0>
-__global__ __launch_bounds__(WI * WJ * 64, WI * WJ > 4 ? 1 : 2)
+          int TJ = 2, int WI = 2, int WJ = 2>
+__global__ __launch_bounds__(WI * WJ * 64, 2)
 void gemm_wgrad_tr_kernel(
     const T16* __restrict__ dy, const T16* __restrict__ x,
     float* __restrict__ dw, const T16* __restrict__ zpad, int Mtot,
@@ -587,12 +414,10 @@ void gemm_wgrad_tr_kernel(
   constexpr int AIMGS = BI / 16, BIMGS = BJ / 16;
   constexpr int TILE_A = AIMGS * IMG, TILE_B = BIMGS * IMG;
   constexpr int NUNITS = AIMGS + TAPS * BIMGS;  // glds image stages / chunk
-  static_assert(NBUF == 2 || NUNITS % (WI * WJ) == 0,
-                "counted vmcnt waits need a uniform per-wave glds count");
   typedef short v4s __attribute__((ext_vector_type(4)));
   using vec16 = typename M16<T16>::vec;
   __shared__ __attribute__((aligned(16)))
-      T16 lds[NBUF * (TILE_A + TAPS * TILE_B)];
+      T16 lds[2 * (TILE_A + TAPS * TILE_B)];
 
   // XCD-contiguous remap: the 8 XCDs have PRIVATE 4 MB L2s, and the default
   // round-robin dispatch places the `tiles` blocks that share a zidx (same
@@ -718,138 +543,16 @@ void gemm_wgrad_tr_kernel(
   ((unsigned)(unsigned long long)(__attribute__((            \
       address_space(3))) const T16*)(p))
 
-  constexpr int PER_WAVE_GLDS = (NUNITS + WI * WJ - 1) / (WI * WJ);
-  // wait until at most `n` STAGES are still in flight (exact count: waiting
-  // for more than are actually outstanding would let an older, unlanded
-  // stage through)
-  auto wg_wait_stages = [&](int n) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    switch (n) {
-      case 0:
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        break;
-      case 1:
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER_WAVE_GLDS) : "memory");
-        break;
-      case 2:
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * PER_WAVE_GLDS)
-                     : "memory");
-        break;
-      default:
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(3 * PER_WAVE_GLDS)
-                     : "memory");
-        break;
-    }
-  };
-
   stage(0, ch0);
-  if (NBUF >= 3) {
-    // fill the prefetch pipeline NBUF-1 deep, then wait for stage 0 only
-    int issued = 1;
-    for (int p = 1; p < NBUF - 1 && ch0 + p < ch1; ++p) {
-      stage(p, ch0 + p);
-      ++issued;
-    }
-    wg_wait_stages(issued - 1);
-    asm volatile("s_barrier" ::: "memory");
-  } else {
-    __syncthreads();
-  }
+  __syncthreads();
 
   constexpr int TI32 = TI / WI, TJ32 = TJ / WJ;
   float bsum[TI32] = {};
   for (int ch = ch0; ch < ch1; ++ch) {
-    const int buf = (ch - ch0) % NBUF;
+    const int buf = (ch - ch0) % 2;
     const bool more = ch + 1 < ch1;
-    if (NBUF >= 3) {
-      if (ch + NBUF - 1 < ch1)
-        stage((ch - ch0 + NBUF - 1) % NBUF, ch + NBUF - 1);
-    } else if (more) {
-      stage(buf ^ 1, ch + 1);  // glds latency hides under the MFMAs
-    }
+    if (more) stage(buf ^ 1, ch + 1);  // glds latency hides under the MFMAs
     const T16* base = lds + buf * (TILE_A + TAPS * TILE_B);
-
-    if constexpr (FUSE && TAPS == 1 && TI / WI == 2 && TJ / WJ == 2) {
-      // Fused-issue path: all 16 tr reads of the chunk go out in ONE asm
-      // block with a single lgkmcnt wait.  The generic path below pays a
-      // full lgkmcnt(0) drain per 4-read fragment block (4 serial LDS
-      // round-trips per chunk against only 8 MFMAs) — PMC showed the plain
-      // TN kernel wait-bound at ~6x SQ_BUSY with the MFMA pipe 16% busy.
-      const T16* tb = base + TILE_A;
-      const unsigned a0 =
-          LDS_BYTE(base + ((wm >> 4) + img_sel) * IMG) + tr_lane_off;
-      const unsigned a1 =
-          LDS_BYTE(base + ((wm >> 4) + 2 + img_sel) * IMG) + tr_lane_off;
-      const unsigned b0 =
-          LDS_BYTE(tb + ((wn >> 4) + img_sel) * IMG) + tr_lane_off;
-      const unsigned b1 =
-          LDS_BYTE(tb + ((wn >> 4) + 2 + img_sel) * IMG) + tr_lane_off;
-      v4s r[16];
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %16 offset:0\n\t"
-          "ds_read_b64_tr_b16 %1, %16 offset:128\n\t"
-          "ds_read_b64_tr_b16 %2, %16 offset:512\n\t"
-          "ds_read_b64_tr_b16 %3, %16 offset:640\n\t"
-          "ds_read_b64_tr_b16 %4, %17 offset:0\n\t"
-          "ds_read_b64_tr_b16 %5, %17 offset:128\n\t"
-          "ds_read_b64_tr_b16 %6, %17 offset:512\n\t"
-          "ds_read_b64_tr_b16 %7, %17 offset:640\n\t"
-          "ds_read_b64_tr_b16 %8, %18 offset:0\n\t"
-          "ds_read_b64_tr_b16 %9, %18 offset:128\n\t"
-          "ds_read_b64_tr_b16 %10, %18 offset:512\n\t"
-          "ds_read_b64_tr_b16 %11, %18 offset:640\n\t"
-          "ds_read_b64_tr_b16 %12, %19 offset:0\n\t"
-          "ds_read_b64_tr_b16 %13, %19 offset:128\n\t"
-          "ds_read_b64_tr_b16 %14, %19 offset:512\n\t"
-          "ds_read_b64_tr_b16 %15, %19 offset:640\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]),
-            "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7]), "=&v"(r[8]), "=&v"(r[9]),
-            "=&v"(r[10]), "=&v"(r[11]), "=&v"(r[12]), "=&v"(r[13]),
-            "=&v"(r[14]), "=&v"(r[15])
-          : "v"(a0), "v"(a1), "v"(b0), "v"(b1));
-      vec16 af2[2][2], bf2[2][2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-          reinterpret_cast<v4s*>(&af2[mi][kh])[0] = r[mi * 4 + kh * 2];
-          reinterpret_cast<v4s*>(&af2[mi][kh])[1] = r[mi * 4 + kh * 2 + 1];
-          reinterpret_cast<v4s*>(&bf2[mi][kh])[0] = r[8 + mi * 4 + kh * 2];
-          reinterpret_cast<v4s*>(&bf2[mi][kh])[1] = r[8 + mi * 4 + kh * 2 + 1];
-        }
-      if (colsum && bx == 0 && wn == 0) {
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          float a = 0.f;
-#pragma unroll
-          for (int kh = 0; kh < 2; ++kh) {
-            const vec16 v = af2[mi][kh];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a += (float)v[j];
-          }
-          bsum[mi] += a;
-        }
-      }
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          acc[mi][ni][0] =
-              M16<T16>::mma32(af2[mi][0], bf2[ni][0], acc[mi][ni][0]);
-          acc[mi][ni][0] =
-              M16<T16>::mma32(af2[mi][1], bf2[ni][1], acc[mi][ni][0]);
-        }
-      if (more) {
-        if (NBUF >= 3) {
-          wg_wait_stages(min(ch + NBUF - 1, ch1 - 1) - (ch + 1));
-          asm volatile("s_barrier" ::: "memory");
-        } else {
-          __syncthreads();
-        }
-      }
-      continue;
-    }
 
     // A fragments (dy): per 32-col tile mi, per 16-m half kh
     vec16 af[TI32][2];
@@ -917,16 +620,7 @@ void gemm_wgrad_tr_kernel(
         }
       }
     }
-    if (more) {
-      if (NBUF >= 3) {
-        // only wait for the stage one chunk back; newer prefetches keep
-        // flying through the barrier
-        wg_wait_stages(min(ch + NBUF - 1, ch1 - 1) - (ch + 1));
-        asm volatile("s_barrier" ::: "memory");
-      } else {
-        __syncthreads();  // drains the glds (vmcnt) + publishes buf^1
-      }
-    }
+    if (more) __syncthreads();  // drains the glds (vmcnt) + publishes buf^1
   }
 
 #undef LDS_BYTE
@@ -975,9 +669,8 @@ void gemm_wgrad_tr_kernel(
 // issue/latency-bound at ~425 TF.  128-B rows cut the request count 4x.
 // Everything else (tr-read fragments, f32 atomic writeback, zsplit, XCD
 // remap, optional fused bias grad) matches the kernel above.
-template <typename T16, int TI = 4, int TJ = 4, int WI = 2, int WJ = 2,
-          int MINB = 3>
-__global__ __launch_bounds__(WI * WJ * 64, MINB) void gemm_tn_plain_kernel(
+template <typename T16, int TI = 4, int TJ = 4, int WI = 2, int WJ = 2>
+__global__ __launch_bounds__(WI * WJ * 64, 3) void gemm_tn_plain_kernel(
     const T16* __restrict__ dy, const T16* __restrict__ x,
     float* __restrict__ dw, const T16* __restrict__ zpad, int Mtot, int I,
     int J, long long ldc, long long sA, long long sB, long long sC,
@@ -1203,127 +896,47 @@ void launch_nt16(const torch::Tensor& A, const torch::Tensor& B,
                  g16::ConvMeta cm, NtExtras ex = {},
                  bool wide_default = false) {
   auto stream = c10::hip::getCurrentHIPStream();
-  const t16* bias_p =
-      bias.has_value() ? reinterpret_cast<const t16*>(bias->data_ptr())
-                       : nullptr;
+  const t16* bias_p = bias.has_value() ? ptr16<t16>(*bias) : nullptr;
   // narrow-N variant: BNT=64 halves the B tile so no MFMA computes
   // zero-page columns (ResNet layer1 Kout=64 fwd, C=64 dgrads).
   const bool narrow = N <= 64;
   if (narrow) grid.x = (N + 63) / 64;
   // wide-N variant: BNT=256 halves the A-operand re-reads and doubles the
-  // MFMAs per barrier window.  Measured: NEUTRAL on plain linear shapes
-  // (510 vs 525 TF on ViT mlp1 — the 73.7 KB LDS drops co-residency and
-  // cancels the traffic win) but a clear WIN for the conv modes where the
-  // A side is an im2col gather that is expensive to re-read: ResNet-18
-  // bench 106.2k -> 108.4k, ResNet-50 7621 -> 8006 samples/s.  Default:
-  // on for conv modes with Kout >= 256, off for MODE_PLAIN.
-  // PDT_NT_BN=256 / 128 forces on / off for A/B runs.
-  static const char* e_ntbn = getenv("PDT_NT_BN");
+  // MFMAs per barrier window.  ON only where the call site asks (conv
+  // FORWARD — the A side is an im2col gather that is expensive to re-read);
+  // neutral on plain linear shapes and a loss on dgrads.
   // NOTE: the epilogue-extras instantiations (stats workspace / residual
   // addend — the fused conv+BN path) are built at BNT=128 only, so wide-N
   // must not halve their grid: doing so left half of C unwritten
   // (uninitialized-memory NaNs from the second step on — found by the
   // round-2 step-1 NaN bisect, tools/graph_dbg2.py).
-  const bool extras_early = ex.stats_ws != nullptr || ex.addend != nullptr;
-  // Post-fix defaults: ON only where the call site asks (conv FORWARD
-  // without epilogue extras — the im2col A-side re-read argument and the
-  // ViT patchify win are real there).  The round-2 blanket conv-mode
-  // "win" was an artifact of the unwritten-half-of-C bug above; with the
-  // grid corrected, wide-N on DGRADs loses e2e (r18 103.0k vs 105.8k).
-  const bool wide_n = (e_ntbn ? e_ntbn[0] == '2' : wide_default) &&
-                      !narrow && !extras_early && N >= 256 && M >= 4096;
-  if (wide_n) grid.x = (N + 255) / 256;
-  // 2-buffer wide-N: same 49 KB footprint as BNT=128x3buf (unchanged
-  // co-residency) with 2x the MFMAs per barrier window.  PDT_NT_NBUF2=1.
-  static const char* e_nb2 = getenv("PDT_NT_NBUF2");
-  const bool ntbuf2 = e_nb2 && e_nb2[0] == '1';
   const bool extras = ex.stats_ws != nullptr || ex.addend != nullptr;
+  const bool wide_n =
+      wide_default && !narrow && !extras && N >= 256 && M >= 4096;
+  if (wide_n) grid.x = (N + 255) / 256;
+#define NT16_KERN(RELU, HB)                                          \
+  (narrow   ? &g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB, 64>     \
+   : wide_n ? &g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB, 256>    \
+            : &g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB>)
+  auto kern = NT16_KERN(false, false);
   if (extras) {
     TORCH_CHECK(!relu && !bias_p,
                 "epilogue extras only instantiated for relu=false, bias=none");
-    if (narrow)
-      hipLaunchKernelGGL(
-          (g16::gemm_nt_bf16_kernel<t16, MODE, false, false, 64, true>), grid,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()),
-          reinterpret_cast<t16*>(C.data_ptr()), nullptr,
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, N, K, sA, sB, sC,
-          cm, ex.stats_ws, ex.ws_nblocks,
-          reinterpret_cast<const t16*>(ex.addend),
-          reinterpret_cast<const t16*>(ex.addend_mask));
-    else
-      hipLaunchKernelGGL(
-          (g16::gemm_nt_bf16_kernel<t16, MODE, false, false, g16::BN, true>),
-          grid, dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()),
-          reinterpret_cast<t16*>(C.data_ptr()), nullptr,
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, N, K, sA, sB, sC,
-          cm, ex.stats_ws, ex.ws_nblocks,
-          reinterpret_cast<const t16*>(ex.addend),
-          reinterpret_cast<const t16*>(ex.addend_mask));
-    return;
+    kern = narrow
+               ? &g16::gemm_nt_bf16_kernel<t16, MODE, false, false, 64, true>
+               : &g16::gemm_nt_bf16_kernel<t16, MODE, false, false, g16::BN,
+                                           true>;
+  } else if (relu) {
+    kern = bias_p ? NT16_KERN(true, true) : NT16_KERN(true, false);
+  } else if (bias_p) {
+    kern = NT16_KERN(false, true);
   }
-#define LAUNCH_NT16(RELU, HB)                                                 \
-  do {                                                                        \
-    if (narrow)                                                               \
-      hipLaunchKernelGGL((g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB, 64>), \
-                         grid, dim3(g16::THREADS), 0, stream,                 \
-                         reinterpret_cast<const t16*>(A.data_ptr()),          \
-                         reinterpret_cast<const t16*>(B.data_ptr()),          \
-                         reinterpret_cast<t16*>(C.data_ptr()), bias_p,        \
-                         reinterpret_cast<const t16*>(zp.data_ptr()), M, N,   \
-                         K, sA, sB, sC, cm, ex.stats_ws, ex.ws_nblocks,       \
-                         reinterpret_cast<const t16*>(ex.addend),             \
-                         reinterpret_cast<const t16*>(ex.addend_mask));       \
-    else if (wide_n && ntbuf2)                                                \
-      hipLaunchKernelGGL(                                                     \
-          (g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB, 256, false, 2>),     \
-          grid, dim3(g16::THREADS), 0, stream,                                \
-          reinterpret_cast<const t16*>(A.data_ptr()),                         \
-          reinterpret_cast<const t16*>(B.data_ptr()),                         \
-          reinterpret_cast<t16*>(C.data_ptr()), bias_p,                       \
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, N, K, sA, sB, sC,   \
-          cm, ex.stats_ws, ex.ws_nblocks,                                     \
-          reinterpret_cast<const t16*>(ex.addend),                            \
-          reinterpret_cast<const t16*>(ex.addend_mask));                      \
-    else if (wide_n)                                                          \
-      hipLaunchKernelGGL(                                                     \
-          (g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB, 256>), grid,         \
-          dim3(g16::THREADS), 0, stream,                                      \
-          reinterpret_cast<const t16*>(A.data_ptr()),                         \
-          reinterpret_cast<const t16*>(B.data_ptr()),                         \
-          reinterpret_cast<t16*>(C.data_ptr()), bias_p,                       \
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, N, K, sA, sB, sC,   \
-          cm, ex.stats_ws, ex.ws_nblocks,                                     \
-          reinterpret_cast<const t16*>(ex.addend),                            \
-          reinterpret_cast<const t16*>(ex.addend_mask));                      \
-    else                                                                      \
-      hipLaunchKernelGGL((g16::gemm_nt_bf16_kernel<t16, MODE, RELU, HB>),     \
-                         grid, dim3(g16::THREADS), 0, stream,                 \
-                         reinterpret_cast<const t16*>(A.data_ptr()),          \
-                         reinterpret_cast<const t16*>(B.data_ptr()),          \
-                         reinterpret_cast<t16*>(C.data_ptr()), bias_p,        \
-                         reinterpret_cast<const t16*>(zp.data_ptr()), M, N,   \
-                         K, sA, sB, sC, cm, ex.stats_ws, ex.ws_nblocks,       \
-                         reinterpret_cast<const t16*>(ex.addend),             \
-                         reinterpret_cast<const t16*>(ex.addend_mask));       \
-  } while (0)
-  if (relu) {
-    if (bias_p) LAUNCH_NT16(true, true);
-    else LAUNCH_NT16(true, false);
-  } else {
-    if (bias_p) LAUNCH_NT16(false, true);
-    else LAUNCH_NT16(false, false);
-  }
-#undef LAUNCH_NT16
-}
-
-int log2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return ((1 << l) == v) ? l : -1;
+#undef NT16_KERN
+  hipLaunchKernelGGL(kern, grid, dim3(g16::THREADS), 0, stream, ptr16<t16>(A),
+                     ptr16<t16>(B), ptr16<t16>(C), bias_p, ptr16<t16>(zp), M,
+                     N, K, sA, sB, sC, cm, ex.stats_ws, ex.ws_nblocks,
+                     static_cast<const t16*>(ex.addend),
+                     static_cast<const t16*>(ex.addend_mask));
 }
 
 }  // namespace
@@ -1354,12 +967,10 @@ torch::Tensor bmm_nt_bf16(torch::Tensor A, torch::Tensor B,
   long long sA = batched ? (long long)M * K : 0;
   long long sB = batched ? (long long)N * K : 0;
   long long sC = batched ? (long long)M * N : 0;
-  if (A.scalar_type() == torch::kBFloat16)
-    launch_nt16<bf16, g16::MODE_PLAIN>(A, B, C, bias, relu, zp, grid, M, N, K,
-                                       sA, sB, sC, cm);
-  else
-    launch_nt16<_Float16, g16::MODE_PLAIN>(A, B, C, bias, relu, zp, grid, M,
-                                           N, K, sA, sB, sC, cm);
+  dispatch16(A, [&](auto tag) {
+    launch_nt16<decltype(tag), g16::MODE_PLAIN>(A, B, C, bias, relu, zp, grid,
+                                                M, N, K, sA, sB, sC, cm);
+  });
   return C;
 }
 
@@ -1426,13 +1037,11 @@ std::vector<torch::Tensor> conv2d_fwd_bf16_impl(
     if (stats) return {y, ws};
     return {y};
   }
-  if (x.scalar_type() == torch::kBFloat16)
-    launch_nt16<bf16, g16::MODE_CONV>(x, w, y, bias, relu, zp, grid, M, Kout,
-                                      K, 0, 0, 0, cm, ex, /*wide*/ true);
-  else
-    launch_nt16<_Float16, g16::MODE_CONV>(x, w, y, bias, relu, zp, grid, M,
-                                          Kout, K, 0, 0, 0, cm, ex,
-                                          /*wide*/ true);
+  dispatch16(x, [&](auto tag) {
+    launch_nt16<decltype(tag), g16::MODE_CONV>(x, w, y, bias, relu, zp, grid,
+                                               M, Kout, K, 0, 0, 0, cm, ex,
+                                               /*wide*/ true);
+  });
   if (stats) return {y, ws};
   return {y};
 }
@@ -1525,12 +1134,10 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
       ex.addend_mask = addend_mask->data_ptr();
     }
   }
-  if (dy.scalar_type() == torch::kBFloat16)
-    launch_nt16<bf16, g16::MODE_CONV>(dy, wr, dx, {}, false, zp, grid, M, Cin,
-                                      K, 0, 0, 0, cm, ex);
-  else
-    launch_nt16<_Float16, g16::MODE_CONV>(dy, wr, dx, {}, false, zp, grid, M,
-                                          Cin, K, 0, 0, 0, cm, ex);
+  dispatch16(dy, [&](auto tag) {
+    launch_nt16<decltype(tag), g16::MODE_CONV>(dy, wr, dx, {}, false, zp, grid,
+                                               M, Cin, K, 0, 0, 0, cm, ex);
+  });
   return masked(dx);
 }
 
@@ -1565,14 +1172,6 @@ torch::Tensor bmm_tn_bf16(torch::Tensor A, torch::Tensor B) {
   // backward has ~1.5K batches; a per-batch host loop dominated its step)
   if (bsz > 1) z = std::max(1, std::min(n_chunks, (int)(2048 / bsz) + 1));
   const bool wide = I >= 128 && J >= 128;  // 128x128 tiles for big GEMMs
-  // 256x256 tiles on 8 waves for the really big shapes: halves the per-
-  // operand HBM re-reads (the 128x128 traffic roofline measured ~450-510 TF
-  // on the ViT wgrad shapes — the same band rocBLAS hits).
-  // PDT_TN_TILE=256 forces the 256 route (A/B measurements); default keeps
-  // the measured-faster 128 tiles.
-  static const char* tn_tile = getenv("PDT_TN_TILE");
-  const bool xwide = (tn_tile && tn_tile[0] == '2') && I >= 256 && J >= 256 &&
-                     M >= 4096;
   if (wide) {
     tiles = ((J + 127) / 128) * ((I + 127) / 128);
     // measured z sweep (ViT wgrad shapes, 1xMI355X): ~1024 blocks (= 2 full
@@ -1585,63 +1184,25 @@ torch::Tensor bmm_tn_bf16(torch::Tensor A, torch::Tensor B) {
     static const char* e_z = getenv("PDT_TN_Z");  // split-M sweep knob
     if (e_z && bsz == 1) z = std::max(1, std::min(n_chunks, atoi(e_z)));
   }
-  if (xwide) {
-    // one 512-thread WG per CU: target ~256 resident blocks (one full round)
-    tiles = ((J + 255) / 256) * ((I + 255) / 256);
-    z = std::max(1, std::min(n_chunks, (256 + tiles - 1) / std::max(1, tiles)));
-    if (bsz > 1) z = std::max(1, std::min(n_chunks, (int)(1024 / bsz) + 1));
-  }
-  auto run = [&](auto tag) {
+  dispatch16(A, [&](auto tag) {
     using t16 = decltype(tag);
-    if (xwide) {
-      dim3 grid((J + 255) / 256, (I + 255) / 256, (unsigned)(bsz * z));
-      hipLaunchKernelGGL(
-          (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN, 8, 8, 2, 4, 3>),
-          grid, dim3(512), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J,
-          /*ldc=*/J, cm, (long long)M * I, (long long)M * J,
-          (long long)I * J, z);
-      return;
-    }
+    const t16 *Ap = ptr16<t16>(A), *Bp = ptr16<t16>(B), *zpp = ptr16<t16>(zp);
+    const long long sA = (long long)M * I, sB = (long long)M * J,
+                    sC = (long long)I * J;
     if (wide) {
       dim3 grid((J + 127) / 128, (I + 127) / 128, (unsigned)(bsz * z));
-      // PDT_TN_KERN=old falls back to the [32m][16ch]-image kernel (A/B)
-      static const char* e_kern = getenv("PDT_TN_KERN");
-      if (e_kern && e_kern[0] == 'o') {
-        hipLaunchKernelGGL(
-            (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN, 4, 4>), grid,
-            dim3(g16::THREADS), 0, stream,
-            reinterpret_cast<const t16*>(A.data_ptr()),
-            reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-            reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J,
-            /*ldc=*/J, cm, (long long)M * I, (long long)M * J,
-            (long long)I * J, z);
-        return;
-      }
-      hipLaunchKernelGGL(
-          (g16::gemm_tn_plain_kernel<t16, 4, 4, 2, 2>), grid,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J,
-          /*ldc=*/J, (long long)M * I, (long long)M * J, (long long)I * J, z,
-          nullptr);
-      return;
+      hipLaunchKernelGGL(g16::gemm_tn_plain_kernel<t16>, grid,
+                         dim3(g16::THREADS), 0, stream, Ap, Bp,
+                         C.data_ptr<float>(), zpp, M, I, J, /*ldc=*/J, sA, sB,
+                         sC, z, nullptr);
+    } else {
+      dim3 grid((J + 63) / 64, (I + 63) / 64, (unsigned)(bsz * z));
+      hipLaunchKernelGGL((g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN>),
+                         grid, dim3(g16::THREADS), 0, stream, Ap, Bp,
+                         C.data_ptr<float>(), zpp, M, I, J, /*ldc=*/J, cm, sA,
+                         sB, sC, z, nullptr);
     }
-    dim3 grid((J + 63) / 64, (I + 63) / 64, (unsigned)(bsz * z));
-    hipLaunchKernelGGL(
-        (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN>), grid,
-        dim3(g16::THREADS), 0, stream,
-        reinterpret_cast<const t16*>(A.data_ptr()),
-        reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-        reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J,
-        /*ldc=*/J, cm, (long long)M * I, (long long)M * J, (long long)I * J,
-        z);
-  };
-  if (A.scalar_type() == torch::kBFloat16) run(bf16{});
-  else run(_Float16{});
+  });
   return C;
 }
 
@@ -1666,69 +1227,28 @@ std::vector<torch::Tensor> bmm_tn_bias_bf16(torch::Tensor A, torch::Tensor B) {
   int n_chunks = (M + 31) / 32;
   g16::ConvMeta cm{};
   auto& zp = zero_page(A.device(), A.scalar_type());
-  static const char* tn_tile2 = getenv("PDT_TN_TILE");
-  // 256x256 tiles on the 128-B-row tn_plain kernel (PDT_TN_TILE=3):
-  // measured SLOWER than 128 tiles (qkv 380 vs 414 TF, proj 219 vs 352 —
-  // the drop to one 8-wave block/CU costs more than the halved re-read
-  // traffic, which the per-XCD L2s largely absorb).  Kept as a documented
-  // negative result; '2' = the older xwide TR route (also slower).
-  const bool xwide = (tn_tile2 && tn_tile2[0] == '2') && I >= 256 &&
-                     J >= 256 && M >= 4096;
-  const bool big256 = (tn_tile2 && tn_tile2[0] == '3') && I >= 256 &&
-                      J >= 256 && M >= 4096;
   const bool wide = I >= 128 && J >= 128;
-  int tiles = (xwide || big256) ? ((J + 255) / 256) * ((I + 255) / 256)
-              : wide ? ((J + 127) / 128) * ((I + 127) / 128)
-                     : ((J + 63) / 64) * ((I + 63) / 64);
+  int tiles = wide ? ((J + 127) / 128) * ((I + 127) / 128)
+                   : ((J + 63) / 64) * ((I + 63) / 64);
   int z = std::max(
-      1, std::min(n_chunks,
-                  ((xwide ? 256 : 1024) + tiles - 1) / std::max(1, tiles)));
-  auto run = [&](auto tag) {
+      1, std::min(n_chunks, (1024 + tiles - 1) / std::max(1, tiles)));
+  dispatch16(A, [&](auto tag) {
     using t16 = decltype(tag);
-    if (big256) {
-      dim3 grid((J + 255) / 256, (I + 255) / 256, (unsigned)z);
-      hipLaunchKernelGGL(
-          (g16::gemm_tn_plain_kernel<t16, 8, 8, 2, 4, 1>), grid,
-          dim3(512), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J, J, 0, 0,
-          0, z, db.data_ptr<float>());
-      return;
-    }
-    if (xwide) {
-      dim3 grid((J + 255) / 256, (I + 255) / 256, (unsigned)z);
-      hipLaunchKernelGGL(
-          (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN, 8, 8, 2, 4, 3>),
-          grid, dim3(512), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J, J, cm, 0, 0,
-          0, z, db.data_ptr<float>());
-      return;
-    }
+    const t16 *Ap = ptr16<t16>(A), *Bp = ptr16<t16>(B), *zpp = ptr16<t16>(zp);
     if (wide) {
       dim3 grid((J + 127) / 128, (I + 127) / 128, (unsigned)z);
-      hipLaunchKernelGGL(
-          (g16::gemm_tn_plain_kernel<t16, 4, 4, 2, 2>), grid,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J, J, 0, 0,
-          0, z, db.data_ptr<float>());
+      hipLaunchKernelGGL(g16::gemm_tn_plain_kernel<t16>, grid,
+                         dim3(g16::THREADS), 0, stream, Ap, Bp,
+                         C.data_ptr<float>(), zpp, M, I, J, /*ldc=*/J, 0, 0, 0,
+                         z, db.data_ptr<float>());
     } else {
       dim3 grid((J + 63) / 64, (I + 63) / 64, (unsigned)z);
-      hipLaunchKernelGGL(
-          (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN>), grid,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(A.data_ptr()),
-          reinterpret_cast<const t16*>(B.data_ptr()), C.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, I, J, J, cm, 0, 0,
-          0, z, db.data_ptr<float>());
+      hipLaunchKernelGGL((g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_PLAIN>),
+                         grid, dim3(g16::THREADS), 0, stream, Ap, Bp,
+                         C.data_ptr<float>(), zpp, M, I, J, /*ldc=*/J, cm, 0,
+                         0, 0, z, db.data_ptr<float>());
     }
-  };
-  if (A.scalar_type() == torch::kBFloat16) run(bf16{});
-  else run(_Float16{});
+  });
   return {C, db};
 }
 
@@ -1745,19 +1265,13 @@ namespace g16 {
 // (E = G*(L+2) <= 48 rows, image padded to 64 so each is exactly 2 glds).
 // A fragment m-window of 4 always sits inside one segment (L >= 4, windows
 // 4-aligned); the second tr read's row jump is L>=8 ? +4 : +6 (uniform).
-// TSPLIT=3: the 9-tap accumulator set is split by kernel ROW across a
-// 12-wave block (wave = rt * 4 + quadrant) — 48 acc VGPRs per wave instead
-// of 144 lifts occupancy 2 -> 3 waves/SIMD, and each wave reads only its
-// own rt's x tiles (per-CU tr-read traffic -40%).  dw writes were already
-// atomicAdd, so the rt-partials need no extra reduction.
-// RSHIFT (TSPLIT==1 only): rolling x-tile ring.  One chunk advances the
+// RSHIFT: rolling x-tile ring.  One chunk advances the
 // output row by RSHIFT (= 32/WO), so chunk ch+1's kernel-row-r tile IS
 // chunk ch's row r+RSHIFT tile — a (3+RSHIFT)-slot ring restages RSHIFT
 // tiles per chunk instead of three (WO=32: 12 glds vs 28; WO=16: 20),
 // except at image boundaries (full restage behind an extra barrier).
-template <typename T16, int TSPLIT = 1, int RSHIFT = 0>
-__global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
-                             TSPLIT == 3 ? 1 : 2) void gemm_wgrad_seg_kernel(
+template <typename T16, int RSHIFT = 0>
+__global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
     const T16* __restrict__ dy, const T16* __restrict__ x,
     float* __restrict__ dw, const T16* __restrict__ zpad, int Mtot,
     int I /*Kout*/, int J /*Cin*/, long long ldc, ConvMeta cm, int lgWO,
@@ -1806,9 +1320,7 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int w4 = TSPLIT == 3 ? (wave & 3) : wave;
-  const int rtw = TSPLIT == 3 ? (wave >> 2) : 0;  // this wave's kernel row
-  const int wm = (w4 >> 1) * 32, wn = (w4 & 1) * 32;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int sm = lane >> 1;
   const int sh8 = (lane & 1) * 8;
   const int L = min(32, 1 << lgWO);  // seg length (pow2)
@@ -1817,7 +1329,7 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
   const int E = segs * (L + 2);
   const int rcpL2 = 65536 / (L + 2) + 1;  // magic recip (q <= 63)
 
-  f32x16 acc[TSPLIT == 3 ? 3 : 9] = {};
+  f32x16 acc[9] = {};
 
   // ---- stage chunk: dy (4 glds) + 3 x row-tiles (8 glds each) ----
   // RING helpers: dy buffers at lds[0..2*TILE_A), x slots after
@@ -1872,7 +1384,7 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
     if (RING) return;
     const int m0 = ch * BMC;
     T16* base = lds + buf * (TILE_A + 3 * TILE_X);
-    for (int u = wave; u < 4 + 24; u += (TSPLIT == 3 ? 12 : 4)) {
+    for (int u = wave; u < 4 + 24; u += 4) {
       const T16* src = zpad;
       T16* dst;
       if (u < 4) {  // dy image u
@@ -1994,9 +1506,9 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
       // async LDS write inside the in-flight MFMA's source-read window —
       // WAR hazard, caught by the cold-launch stress test)
       v4s pb[3][2];
-      constexpr int NPAIR = TSPLIT == 3 ? 6 : 18;
+      constexpr int NPAIR = 18;
       auto issueB = [&](int slot, int idx) {
-        const int rt = TSPLIT == 3 ? rtw : idx / 6;
+        const int rt = idx / 6;
         const int rem = idx % 6, s2 = rem >> 1, kh = rem & 1;
         const T16* timg =
             RING ? lds + 2 * TILE_A + ((r0 + rt) % SLOTS) * TILE_X +
@@ -2027,7 +1539,7 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
           asm volatile("s_waitcnt lgkmcnt(0)"
                        : "+v"(pb[slot][0]), "+v"(pb[slot][1]));
         }
-        const int rt = TSPLIT == 3 ? 0 : idx / 6;
+        const int rt = idx / 6;
         const int rem = idx % 6, s2 = rem >> 1, kh = rem & 1;
         vec16 bf;
         reinterpret_cast<v4s*>(&bf)[0] = pb[slot][0];
@@ -2051,10 +1563,9 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
     }
   }
 
-  // ---- writeback (32x32x16 C/D layout; TSPLIT: only this wave's taps) ----
+  // ---- writeback (32x32x16 C/D layout) ----
 #pragma unroll
-  for (int t3 = 0; t3 < (TSPLIT == 3 ? 3 : 9); ++t3) {
-    const int tap = TSPLIT == 3 ? rtw * 3 + t3 : t3;
+  for (int tap = 0; tap < 9; ++tap) {
     const long long coff = (long long)tap * Cin;
     const int col = j0 + wn + (lane & 31);
     if (col >= Cin) continue;
@@ -2062,7 +1573,7 @@ __global__ __launch_bounds__(TSPLIT == 3 ? 768 : THREADS,
     for (int reg = 0; reg < 16; ++reg) {
       const int row = i0 + wm + (reg & 3) + 8 * (reg >> 2) + 4 * ks;
       if (row >= I) continue;
-      atomicAdd(&dw[(long long)row * ldc + coff + col], acc[t3][reg]);
+      atomicAdd(&dw[(long long)row * ldc + coff + col], acc[tap][reg]);
     }
   }
 }
@@ -2106,113 +1617,58 @@ torch::Tensor conv2d_wgrad_bf16(torch::Tensor dy, torch::Tensor x,
                    std::min(n_chunks, (btarget + tiles - 1) / std::max(1, tiles)));
   const long long ldc = (long long)R * S * Cin;
   dim3 grid((Cin + 63) / 64, (Kout + 63) / 64, z);
-  auto pow2l = [](int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return ((1 << l) == v && v >= 4) ? l : -1;
-  };
-  const int lgWO = pow2l(WO), lgHO = pow2l(HO);
-  auto run = [&](auto tag) {
+  const int lgWO = log2_exact(WO), lgHO = log2_exact(HO);
+  dispatch16(x, [&](auto tag) {
     using t16 = decltype(tag);
+    const t16 *dyp = ptr16<t16>(dy), *xp = ptr16<t16>(x),
+              *zpp = ptr16<t16>(zp);
+    float* dwp = dw.data_ptr<float>();
     if (R == 3 && S == 3 && stride == 1 && lgWO >= 2 && lgHO >= 2) {
-      // segment-staged fast path (stride-1, pow2 spatial): 28 glds/chunk
-      // instead of 40, x gathered once per kernel ROW not per tap.
-      // Measured: the 12-wave rt-split variant (92 VGPR, 3 waves/SIMD,
-      // -40% per-CU tr traffic) LOSES to the 4-wave form (19.5 vs 18.4 ms
-      // summed wgrad; bench 113.8k vs 115.7k) — one 12-wave block
-      // locksteps every wave at the per-chunk barrier, while two 4-wave
-      // blocks interleave around each other's glds drains.  Kept behind
-      // PDT_WGRAD_TSPLIT=3 as a documented negative result.
-      static const char* e_ts = getenv("PDT_WGRAD_TSPLIT");
-      // rolling-ring x reuse (WO==32): default ON — L1 wgrad 1.30 ->
+      // segment-staged fast path (stride-1, pow2 spatial >= 4): 28
+      // glds/chunk instead of 40, x gathered once per kernel ROW not per tap.
+      // rolling-ring x reuse (WO >= 16): default ON — L1 wgrad 1.30 ->
       // 0.94 ms (+38%), r18 bench 114.9k -> 118.8k same-box.
       // PDT_WGRAD_RING=0 reverts.
       static const char* e_rg = getenv("PDT_WGRAD_RING");
       const bool ring =
           !(e_rg && e_rg[0] == '0') && lgWO >= 4 && lgHO >= 1;
-      if (ring && lgWO == 5) {
-        hipLaunchKernelGGL((g16::gemm_wgrad_seg_kernel<t16, 1, 1>), grid,
-                           dim3(g16::THREADS), 0, stream,
-                           reinterpret_cast<const t16*>(dy.data_ptr()),
-                           reinterpret_cast<const t16*>(x.data_ptr()),
-                           dw.data_ptr<float>(),
-                           reinterpret_cast<const t16*>(zp.data_ptr()), M,
-                           Kout, Cin, ldc, cm, lgWO, lgHO, (int)grid.z);
-      } else if (ring && lgWO == 4) {
-        hipLaunchKernelGGL((g16::gemm_wgrad_seg_kernel<t16, 1, 2>), grid,
-                           dim3(g16::THREADS), 0, stream,
-                           reinterpret_cast<const t16*>(dy.data_ptr()),
-                           reinterpret_cast<const t16*>(x.data_ptr()),
-                           dw.data_ptr<float>(),
-                           reinterpret_cast<const t16*>(zp.data_ptr()), M,
-                           Kout, Cin, ldc, cm, lgWO, lgHO, (int)grid.z);
-      } else if (e_ts && e_ts[0] == '3')
-        hipLaunchKernelGGL((g16::gemm_wgrad_seg_kernel<t16, 3>), grid,
-                           dim3(768), 0, stream,
-                           reinterpret_cast<const t16*>(dy.data_ptr()),
-                           reinterpret_cast<const t16*>(x.data_ptr()),
-                           dw.data_ptr<float>(),
-                           reinterpret_cast<const t16*>(zp.data_ptr()), M,
-                           Kout, Cin, ldc, cm, lgWO, lgHO, (int)grid.z);
-      else
-        hipLaunchKernelGGL((g16::gemm_wgrad_seg_kernel<t16>), grid,
-                           dim3(g16::THREADS), 0, stream,
-                           reinterpret_cast<const t16*>(dy.data_ptr()),
-                           reinterpret_cast<const t16*>(x.data_ptr()),
-                           dw.data_ptr<float>(),
-                           reinterpret_cast<const t16*>(zp.data_ptr()), M,
-                           Kout, Cin, ldc, cm, lgWO, lgHO, (int)grid.z);
-    } else if (R == 3 && S == 3) {
-      hipLaunchKernelGGL((g16::gemm_wgrad_tr_kernel<t16, 9>), grid,
-                         dim3(g16::THREADS), 0, stream,
-                         reinterpret_cast<const t16*>(dy.data_ptr()),
-                         reinterpret_cast<const t16*>(x.data_ptr()),
-                         dw.data_ptr<float>(),
-                         reinterpret_cast<const t16*>(zp.data_ptr()), M, Kout,
-                         Cin, ldc, cm, 0, 0, 0, (int)grid.z);
-    } else if (R == 1 && S == 1 && Kout >= 128 && Cin >= 128) {
+      auto kern = ring && lgWO == 5   ? &g16::gemm_wgrad_seg_kernel<t16, 1>
+                  : ring && lgWO == 4 ? &g16::gemm_wgrad_seg_kernel<t16, 2>
+                                      : &g16::gemm_wgrad_seg_kernel<t16>;
+      hipLaunchKernelGGL(kern, grid, dim3(g16::THREADS), 0, stream, dyp, xp,
+                         dwp, zpp, M, Kout, Cin, ldc, cm, lgWO, lgHO,
+                         (int)grid.z);
+      return;
+    }
+    auto kern = &g16::gemm_wgrad_tr_kernel<t16, 9>;  // the other 3x3s
+    int J = Cin;
+    if (R == 1 && S == 1 && Kout >= 128 && Cin >= 128) {
       // wide 128x128 tiles: the bottleneck 1x1s (up to 512x2048 dw) re-read
       // dy grid.x times; halving grid.x halves that traffic
       int tiles2 = ((Cin + 127) / 128) * ((Kout + 127) / 128);
       int z2 = std::max(
           1,
           std::min(n_chunks, (btarget + tiles2 - 1) / std::max(1, tiles2)));
-      dim3 grid2((Cin + 127) / 128, (Kout + 127) / 128, (unsigned)z2);
-      hipLaunchKernelGGL(
-          (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_CONV, 4, 4>), grid2,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(dy.data_ptr()),
-          reinterpret_cast<const t16*>(x.data_ptr()), dw.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, Kout, Cin, ldc, cm,
-          0, 0, 0, z2);
+      grid = dim3((Cin + 127) / 128, (Kout + 127) / 128, (unsigned)z2);
+      kern = &g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_CONV, 4, 4>;
     } else if (R == 1 && S == 1) {
-      hipLaunchKernelGGL((g16::gemm_wgrad_tr_kernel<t16, 1>), grid,
-                         dim3(g16::THREADS), 0, stream,
-                         reinterpret_cast<const t16*>(dy.data_ptr()),
-                         reinterpret_cast<const t16*>(x.data_ptr()),
-                         dw.data_ptr<float>(),
-                         reinterpret_cast<const t16*>(zp.data_ptr()), M, Kout,
-                         Cin, ldc, cm, 0, 0, 0, (int)grid.z);
-    } else {  // generic R x S: taps-on-J, ONE launch (dw[I][R*S*Cin] as a
+      kern = &g16::gemm_wgrad_tr_kernel<t16, 1>;
+    } else if (R != 3 || S != 3) {
+      // generic R x S: taps-on-J, ONE launch (dw[I][R*S*Cin] as a
       // single TN GEMM; col j = tap*Cin + c gathers x at tap's shift).
       // The per-tap TN alternative re-read all of dy R*S times — the 7x7
       // ResNet-50 stem spent 13.4 ms/step (28% of the step) there.
-      const int Jl = (int)ldc;  // = R*S*Cin
-      int tiles2 = ((Jl + 127) / 128) * ((Kout + 63) / 64);
+      J = (int)ldc;  // = R*S*Cin
+      int tiles2 = ((J + 127) / 128) * ((Kout + 63) / 64);
       int z2 = std::max(
           1,
           std::min(n_chunks, (btarget + tiles2 - 1) / std::max(1, tiles2)));
-      dim3 grid2((Jl + 127) / 128, (Kout + 63) / 64, (unsigned)z2);
-      hipLaunchKernelGGL(
-          (g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_CONVJ, 2, 4>), grid2,
-          dim3(g16::THREADS), 0, stream,
-          reinterpret_cast<const t16*>(dy.data_ptr()),
-          reinterpret_cast<const t16*>(x.data_ptr()), dw.data_ptr<float>(),
-          reinterpret_cast<const t16*>(zp.data_ptr()), M, Kout, Jl, ldc, cm,
-          0, 0, 0, z2);
+      grid = dim3((J + 127) / 128, (Kout + 63) / 64, (unsigned)z2);
+      kern = &g16::gemm_wgrad_tr_kernel<t16, 1, g16::MODE_CONVJ, 2, 4>;
     }
-  };
-  if (x.scalar_type() == torch::kBFloat16) run(bf16{});
-  else run(_Float16{});
+    hipLaunchKernelGGL(kern, grid, dim3(g16::THREADS), 0, stream, dyp, xp, dwp,
+                       zpp, M, Kout, J, ldc, cm, 0, 0, 0, (int)grid.z,
+                       nullptr);
+  });
   return dw;
 }

@@ -75,6 +75,25 @@ def test_gemm_nt_bf16_bias_relu():
     close_bf16(out, ref, scale=6.0)
 
 
+@pytest.mark.parametrize("use_bias,relu",
+                         [(True, True), (True, False), (False, True)])
+def test_gemm_nt_bf16_plain256_epilogues(use_bias, relu):
+    # the bias / relu instantiations of the 256x256-tile glds kernel
+    # (gemm_plain.hip); the plain one is test_gemm_nt_bf16[4096-256-128]
+    m, n, k = 4096, 256, 64
+    a = t32(m, k, seed=1).to(torch.bfloat16)
+    b = t32(n, k, seed=2).to(torch.bfloat16)
+    bias = t32(n, seed=5).to(torch.bfloat16)
+    out = EXT.gemm_nt(a.to(DEV), b.to(DEV), bias.to(DEV) if use_bias else None,
+                      relu, False)
+    ref = a.float() @ b.float().t()
+    if use_bias:
+        ref = ref + bias.float()
+    if relu:
+        ref = torch.relu(ref)
+    close_bf16(out, ref, scale=float(k) ** 0.5)
+
+
 @pytest.mark.parametrize("m,n,k", [(64, 64, 64), (128, 96, 132), (33, 17, 8)])
 def test_gemm_nt_f32(m, n, k):
     a = t32(m, k, seed=6)
@@ -85,7 +104,8 @@ def test_gemm_nt_f32(m, n, k):
 
 @pytest.mark.parametrize("m,i,j", [(256, 64, 64), (1000, 70, 33), (64, 10, 512),
                                    (512, 256, 384), (2048, 768, 768),
-                                   # 256x256-tile 8-wave route (xwide)
+                                   # big ViT wgrad shapes: 128-tile
+                                   # gemm_tn_plain_kernel, z-split
                                    (8192, 768, 768), (8192, 2304, 768),
                                    (5000, 300, 260)])
 def test_gemm_tn_bf16(m, i, j):
@@ -159,8 +179,11 @@ def conv_ref(x, w, stride, pad):
         (2, 8, 128, 64, 1, 1, 0),     # 1x1
         (2, 32, 3, 64, 3, 1, 1),      # stem (im2col fallback)
         (1, 16, 64, 64, 1, 2, 0),     # 1x1 stride-2 (downsample)
-        (16, 16, 256, 256, 3, 1, 1),  # wide-N variant (M>=4096, N>=256)
+        (16, 16, 256, 256, 3, 1, 1),  # glds engine, 256x256 tile
         (64, 14, 64, 64, 3, 1, 1),    # glds path, non-pow2 spatial (r50)
+        # NT wide-N tile (BNT=256: M>=4096, N>=256); C=32 < 64 keeps the
+        # glds engine out and the halo path is 3x3 only
+        (4, 32, 32, 256, 1, 1, 0),
     ],
 )
 def test_conv2d_fwd_bf16(n, h, c, k, r, stride, pad):
@@ -175,7 +198,7 @@ def test_conv2d_fwd_bf16(n, h, c, k, r, stride, pad):
 @pytest.mark.parametrize(
     "n,h,c,k,r,stride,pad",
     [(2, 16, 64, 64, 3, 1, 1), (2, 16, 64, 128, 3, 2, 1), (1, 8, 64, 64, 1, 2, 0),
-     (16, 16, 256, 256, 3, 1, 1),   # wide-N variant (M>=4096, N>=256)
+     (16, 16, 256, 256, 3, 1, 1),   # glds engine, 256x256 tile
      (64, 14, 64, 64, 3, 1, 1),     # glds path, non-pow2 spatial (r50)
      (64, 28, 64, 128, 3, 2, 1)],   # glds stuffed dgrad, non-pow2
 )
@@ -203,7 +226,9 @@ def test_conv2d_dgrad_bf16(n, h, c, k, r, stride, pad):
      # (7x7 s2 p3, Cin-padded-8) and a 5x5 to cover non-square tap counts
      (2, 28, 8, 64, 7, 2, 3), (2, 14, 16, 32, 5, 1, 2),
      # WO=32 (one output row per seg chunk): the rolling-ring reuse domain
-     (4, 32, 64, 64, 3, 1, 1)],
+     (4, 32, 64, 64, 3, 1, 1),
+     # 1x1: the 64-tile route, and the 128-tile route (Kout, Cin >= 128)
+     (2, 8, 128, 64, 1, 1, 0), (2, 8, 128, 128, 1, 1, 0)],
 )
 def test_conv2d_wgrad_bf16(n, h, c, k, r, stride, pad):
     ho = (h + 2 * pad - r) // stride + 1

@@ -1,5 +1,5 @@
 """Single-shape TN wgrad loop for PMC / A-B runs.
-Usage: [PDT_TN_TILE=128|256] python tools/tn_bench.py [I J iters]
+Usage: [PDT_TN_Z=<split>] python tools/tn_bench.py [I J iters]
 """
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,5 +21,5 @@ for _ in range(iters):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / iters
 tf = 2.0 * M * I * J / dt / 1e12
-print(f"TILE={os.environ.get('PDT_TN_TILE','def')} I={I} J={J}: "
+print(f"Z={os.environ.get('PDT_TN_Z','def')} I={I} J={J}: "
       f"{dt*1e3:.3f} ms  {tf:.0f} TF")
