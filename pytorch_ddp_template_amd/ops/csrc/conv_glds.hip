@@ -15,6 +15,10 @@
 // col sums/sumsq) matching the NT/halo workspace convention so the fused
 // conv+BN path (bn_fwd_ws) consumes it unchanged.  Optional dgrad epilogue
 // (skip-grad addend and/or ReLU mask in the coalesced store phase, EPI_*).
+// With EPI_BNSTATS the masked dgrad also leaves the per-channel BatchNorm
+// backward sums (sum dz, sum dz*xhat) of the BN it feeds in a workspace that
+// bn_bwd_finalize_kernel consumes, so that BN's stats pass disappears
+// (bn_bwd_ws) — the backward mirror of the forward stats epilogue.
 //
 // Eligibility (host): bf16, pow2 C >= 64, M % 256 == 0, Kout % 64 == 0.
 // Tiles: BM=256 by BN=256/128/64 (by Kout) — always 8 waves as 2(M)x4(N),
@@ -60,6 +64,12 @@ struct Geom {
 // rounded to bf16 — bit-identical to the separate ew::AddOp / ew::ReluBwdOp
 // passes it replaces.
 constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_MASK = 2, EPI_ADD_MASK = 3;
+// bit 2 = BN-backward sums of the stored (masked) values; only together with
+// the mask and without an addend.  The addend operand slot then carries the
+// BN input t, and for every stored element v (column c)
+//   ws[R + row][c] += v          ws[row][c] += v * (t - mean[c]) * rstd[c]
+// with row = block id % R: the [2R][C] layout of bn_bwd_stats_kernel.
+constexpr int EPI_BNSTATS = 4, EPI_MASK_BNSTATS = EPI_MASK | EPI_BNSTATS;
 
 template <int BN, bool STATS, int EPI = EPI_NONE>
 __global__ __launch_bounds__(THREADS, BN == 64 ? 2 : 1)
@@ -69,8 +79,12 @@ void conv_fwd_glds_kernel(
     int M, int N /*Kout*/, int K /*RSC*/, Geom g,
     float* __restrict__ stats_ws, int ws_nblocks,
     const __hip_bfloat16* __restrict__ addend,
-    const __hip_bfloat16* __restrict__ out_mask) {
-  static_assert(!(STATS && EPI != EPI_NONE), "dgrad epilogues carry no stats");
+    const __hip_bfloat16* __restrict__ out_mask,
+    const float* __restrict__ bn_mean, const float* __restrict__ bn_rstd) {
+  static_assert(!(STATS && EPI != EPI_NONE),
+                "dgrad epilogues carry no forward stats");
+  static_assert(!(EPI & EPI_BNSTATS) || EPI == EPI_MASK_BNSTATS,
+                "BN-backward sums ride only with the mask, without an addend");
   __shared__ __hip_bfloat16 smem[2 * (BM + BN) * BK];
 
   const int tid = threadIdx.x;
@@ -249,13 +263,14 @@ void conv_fwd_glds_kernel(
   // the store loop (never all NR rounds in registers at once).
   constexpr bool HAS_ADD = (EPI & EPI_ADD) != 0;
   constexpr bool HAS_MASK = (EPI & EPI_MASK) != 0;
+  constexpr bool HAS_BNS = (EPI & EPI_BNSTATS) != 0;  // av[] carries t
   constexpr int PF = 2;
   static_assert(NR >= PF, "epilogue prefetch deeper than the store loop");
   short8 av[PF] = {}, mv[PF] = {};
   auto epi_load = [&](int r, int slot) {
     const long long off =
         ((m0 + r * RPR + wrow) * N + n0) * 2 + wchunk * 16;  // bytes
-    if constexpr (HAS_ADD)
+    if constexpr (HAS_ADD || HAS_BNS)
       av[slot] = *(const short8*)((const char*)addend + off);
     if constexpr (HAS_MASK)
       mv[slot] = *(const short8*)((const char*)out_mask + off);
@@ -275,41 +290,136 @@ void conv_fwd_glds_kernel(
         cs[row * BN + col] = f2bf(acc[mi][ni][reg]);
       }
     }
-  __syncthreads();
+  // BN-backward sums: a thread's 8 columns are the same in every store round
+  // (wchunk), so it keeps 2x8 running sums; mean/rstd are fetched only now,
+  // when the MFMA accumulators are dead.
+  float mu[8] = {}, rs[8] = {}, sdg[8] = {}, sdb[8] = {};
+  if constexpr (HAS_BNS) {
 #pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    const int row = r * RPR + wrow;
-    short8 c = *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
-    if constexpr (EPI != EPI_NONE) {
-      const short8 a = av[r % PF], m = mv[r % PF];
-      if (r + PF < NR) epi_load(r + PF, r % PF);
-      // same per-element op chain as ew::binary_kernel<bf16, AddOp> then
-      // <bf16, ReluBwdOp>: fp32 add, RNE to bf16, then 0 where !(mask > 0)
+    for (int j = 0; j < 8; ++j) {
+      mu[j] = bn_mean[n0 + wchunk * 8 + j];
+      rs[j] = bn_rstd[n0 + wchunk * 8 + j];
+    }
+  }
+  __syncthreads();
+  if constexpr (!HAS_BNS) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int row = r * RPR + wrow;
+      short8 c = *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
+      if constexpr (EPI != EPI_NONE) {
+        const short8 a = av[r % PF], m = mv[r % PF];
+        if (r + PF < NR) epi_load(r + PF, r % PF);
+        // same per-element op chain as ew::binary_kernel<bf16, AddOp> then
+        // <bf16, ReluBwdOp>: fp32 add, RNE to bf16, then 0 where !(mask > 0)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          short v = c[j];
+          if constexpr (HAS_ADD) v = f2bfbits(bfbits2f(v) + bfbits2f(a[j]));
+          if constexpr (HAS_MASK)
+            v = f2bfbits(bfbits2f(m[j]) > 0.f ? bfbits2f(v) : 0.f);
+          c[j] = v;
+        }
+      }
+      *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
+    }
+  } else {
+    // Masked store plus the BN-backward sums.  A real loop over pairs of
+    // rounds (one per prefetch slot): unrolled like the loop above, the
+    // addresses of all NR rounds are formed up front, and with the 32 extra
+    // live floats the 256-wide tile spills.
+    static_assert(PF == 2 && NR % PF == 0, "store loop steps by slot pairs");
+    auto store_round = [&](int r, int slot) {
+      const int row = r * RPR + wrow;
+      short8 c = *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
+      const short8 t = av[slot], m = mv[slot];
+      if (r + PF < NR) epi_load(r + PF, slot);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        short v = c[j];
-        if constexpr (HAS_ADD) v = f2bfbits(bfbits2f(v) + bfbits2f(a[j]));
-        if constexpr (HAS_MASK)
-          v = f2bfbits(bfbits2f(m[j]) > 0.f ? bfbits2f(v) : 0.f);
-        c[j] = v;
+        // the stored value, exactly as EPI_MASK stores it; the sums use the
+        // expression of bn_bwd_stats_kernel
+        const float gv = bfbits2f(m[j]) > 0.f ? bfbits2f(c[j]) : 0.f;
+        c[j] = f2bfbits(gv);
+        sdb[j] += gv;
+        sdg[j] += gv * (bfbits2f(t[j]) - mu[j]) * rs[j];
       }
+      *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
+    };
+#pragma unroll 1
+    for (int r = 0; r < NR; r += PF) {
+      store_round(r, 0);
+      store_round(r + 1, 1);
     }
-    *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
+  }
+
+  // ---- BN-backward sums: combine the RPR threads that share a column
+  // group through LDS (the tile buffer is free once every thread has read
+  // its rows), then one atomic per column and sum into the pre-zeroed
+  // workspace.  Consecutive lanes add to consecutive columns of one row.
+  if constexpr (HAS_BNS) {
+    constexpr int P = THREADS / (2 * BN);  // threads per column sum: 4/2/1
+    constexpr int RP = RPR / P;            // rows each of them adds (16)
+    static_assert(P >= 1 && RP * P == RPR, "column reduction split");
+    static_assert((2 * RPR * BN + P * 2 * BN) * sizeof(float) <=
+                      sizeof(smem), "reduction buffers exceed the tile LDS");
+    float* red = reinterpret_cast<float*>(smem);  // [2][RPR][BN]
+    float* red2 = red + 2 * RPR * BN;             // [P][2*BN]
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      red[wrow * BN + wchunk * 8 + j] = sdg[j];
+      red[(RPR + wrow) * BN + wchunk * 8 + j] = sdb[j];
+    }
+    __syncthreads();
+    const int ci = tid % (2 * BN), part = tid / (2 * BN);
+    const int which = ci / BN, col = ci % BN;  // which: 0 = dg, 1 = db
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < RP; ++i)
+      s += red[(which * RPR + part * RP + i) * BN + col];
+    if constexpr (P > 1) {
+      red2[part * 2 * BN + ci] = s;
+      __syncthreads();
+      if (part != 0) return;
+      s = red2[ci];
+#pragma unroll
+      for (int p = 1; p < P; ++p) s += red2[p * 2 * BN + ci];
+    }
+    const long long wsrow = flat_id % ws_nblocks;
+    atomicAdd(&stats_ws[((long long)which * ws_nblocks + wsrow) * N + n0 + col],
+              s);
   }
 }
 
 }  // namespace cg
 
+// BN-backward sums request of a dgrad launch (cg::EPI_BNSTATS): the BN input
+// t, its saved mean / rstd, and where to return the workspace.
+struct GldsBnStats {
+  const torch::Tensor& bn_x;
+  const torch::Tensor& mean;
+  const torch::Tensor& rstd;
+  torch::Tensor ws;  // out: zeroed [2R][C] fp32, R <= kBnStatsRows
+};
+
+// Workspace rows of the BN-backward sums: the 1024 rows bn_bwd's own stats
+// pass uses at most, so bn_bwd_finalize_kernel runs in the launch shape it
+// has today; blocks beyond that wrap (every block adds with atomics).
+constexpr int kBnStatsRows = 1024;
+
 // Host entry: returns true when handled.  y must be pre-allocated
 // [N,HO,WO,Kout]; stats_ws (optional) pre-zeroed [2*ws_nblocks, Kout].
 // addend / out_mask (optional, dgrad only, never with stats_ws): y-shaped
 // contiguous tensors applied in the store phase — see cg::EPI_*.
-bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
-                        torch::Tensor& y, const torch::Tensor& zp,
-                        int64_t stride, int64_t pad, float* stats_ws,
-                        int ws_nblocks, int lgSt,
-                        const c10::optional<torch::Tensor>& addend,
-                        const c10::optional<torch::Tensor>& out_mask) {
+// bns (optional, with out_mask only): also emit the BN-backward sums; the
+// zeroed workspace is allocated here, once the shape is known to be taken.
+static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
+                               torch::Tensor& y, const torch::Tensor& zp,
+                               int64_t stride, int64_t pad, float* stats_ws,
+                               int ws_nblocks, int lgSt,
+                               const c10::optional<torch::Tensor>& addend,
+                               const c10::optional<torch::Tensor>& out_mask,
+                               GldsBnStats* bns) {
   static const char* e = getenv("PDT_CONV_GLDS");
   if (e && e[0] == '0') return false;
   if (x.scalar_type() != torch::kBFloat16) return false;
@@ -342,11 +452,35 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
   }
   const bf16* addp = addend.has_value() ? ptr16<bf16>(*addend) : nullptr;
   const bf16* maskp = out_mask.has_value() ? ptr16<bf16>(*out_mask) : nullptr;
+  const float *meanp = nullptr, *rstdp = nullptr;
+  if (bns) {
+    TORCH_CHECK(epi == cg::EPI_MASK && !stats_ws,
+                "conv glds: BN-backward sums need out_mask and no addend");
+    TORCH_CHECK(bns->bn_x.is_cuda() && bns->bn_x.is_contiguous() &&
+                    bns->bn_x.scalar_type() == x.scalar_type() &&
+                    bns->bn_x.numel() == y.numel(),
+                "conv glds: bn_x must be contiguous, of dy's dtype and "
+                "dx-sized");
+    for (const auto* t : {&bns->mean, &bns->rstd})
+      TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                      t->scalar_type() == torch::kFloat32 &&
+                      t->numel() == Kout,
+                  "conv glds: bn_mean/bn_rstd must be fp32 [C]");
+    ws_nblocks = (int)std::min<long long>(kBnStatsRows,
+                                          (long long)grid.x * grid.y);
+    bns->ws = torch::zeros({2LL * ws_nblocks, Kout},
+                           x.options().dtype(torch::kFloat32));
+    stats_ws = bns->ws.data_ptr<float>();
+    addp = ptr16<bf16>(bns->bn_x);  // rides in the addend operand slot
+    meanp = bns->mean.data_ptr<float>();
+    rstdp = bns->rstd.data_ptr<float>();
+  }
 #define CG_KERN(ST, EP)                                       \
   (BN == 256   ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
    : BN == 128 ? &cg::conv_fwd_glds_kernel<128, ST, EP>       \
                : &cg::conv_fwd_glds_kernel<64, ST, EP>)
-  auto kern = stats_ws                ? CG_KERN(true, cg::EPI_NONE)
+  auto kern = bns                     ? CG_KERN(false, cg::EPI_MASK_BNSTATS)
+              : stats_ws              ? CG_KERN(true, cg::EPI_NONE)
               : epi == cg::EPI_NONE   ? CG_KERN(false, cg::EPI_NONE)
               : epi == cg::EPI_ADD    ? CG_KERN(false, cg::EPI_ADD)
               : epi == cg::EPI_MASK   ? CG_KERN(false, cg::EPI_MASK)
@@ -354,8 +488,34 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
 #undef CG_KERN
   hipLaunchKernelGGL(kern, grid, dim3(cg::THREADS), 0, stream, ptr16<bf16>(x),
                      ptr16<bf16>(w), ptr16<bf16>(y), ptr16<bf16>(zp), (int)M,
-                     Kout, K, g, stats_ws, ws_nblocks, addp, maskp);
+                     Kout, K, g, stats_ws, ws_nblocks, addp, maskp, meanp,
+                     rstdp);
   return true;
+}
+
+bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
+                        torch::Tensor& y, const torch::Tensor& zp,
+                        int64_t stride, int64_t pad, float* stats_ws,
+                        int ws_nblocks, int lgSt,
+                        const c10::optional<torch::Tensor>& addend,
+                        const c10::optional<torch::Tensor>& out_mask) {
+  return conv2d_glds_launch(x, w, y, zp, stride, pad, stats_ws, ws_nblocks,
+                            lgSt, addend, out_mask, nullptr);
+}
+
+// Masked dgrad that also emits the BN-backward sums of the BN it feeds.
+// Returns the workspace ([2R][C]: rows [0,R) sum dz*xhat, [R,2R) sum dz), or
+// an undefined tensor when the kernel declines the shape (nothing launched).
+torch::Tensor conv2d_dgrad_glds_bnstats(
+    const torch::Tensor& dy, const torch::Tensor& wr, torch::Tensor& dx,
+    const torch::Tensor& zp, int64_t pad, int lgSt,
+    const torch::Tensor& out_mask, const torch::Tensor& bn_x,
+    const torch::Tensor& bn_mean, const torch::Tensor& bn_rstd) {
+  GldsBnStats bns{bn_x, bn_mean, bn_rstd, torch::Tensor()};
+  if (!conv2d_glds_launch(dy, wr, dx, zp, 1, pad, nullptr, 0, lgSt,
+                          c10::nullopt, out_mask, &bns))
+    return torch::Tensor();
+  return bns.ws;
 }
 
 bool conv2d_fwd_glds(const torch::Tensor& x, const torch::Tensor& w,

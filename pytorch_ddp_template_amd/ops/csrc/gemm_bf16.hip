@@ -333,7 +333,7 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_bf16_kernel(
     // shuffle reduces them; each wave PAIR (wave>>1 disambiguates waves
     // sharing a column range at different row halves) stores its slice into
     // its own workspace row (ws_nblocks = 2 * grid blocks).
-    // ws rows are capped (host: ws_nblocks <= 8192); blocks beyond the cap
+    // ws rows are capped (host: ws_nblocks <= 2048); blocks beyond the cap
     // wrap around and accumulate atomically (big-M launches would otherwise
     // scale the workspace and its zero-fill/finalize with M)
     const long long vrow = (long long)flat_id * 2 + (wave >> 1);
@@ -989,6 +989,11 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
                         int ws_nblocks, int lgSt,
                         const c10::optional<torch::Tensor>& addend,
                         const c10::optional<torch::Tensor>& out_mask);
+torch::Tensor conv2d_dgrad_glds_bnstats(
+    const torch::Tensor& dy, const torch::Tensor& wr, torch::Tensor& dx,
+    const torch::Tensor& zp, int64_t pad, int lgSt,
+    const torch::Tensor& out_mask, const torch::Tensor& bn_x,
+    const torch::Tensor& bn_mean, const torch::Tensor& bn_rstd);
 // elementwise.hip
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y);
 
@@ -1012,9 +1017,12 @@ std::vector<torch::Tensor> conv2d_fwd_bf16_impl(
   auto& zp = zero_page(x.device(), x.scalar_type());
   dim3 grid((Kout + g16::BN - 1) / g16::BN, (M + g16::BM - 1) / g16::BM, 1);
   // 2 workspace rows per block (per wave-pair; see the epilogue), capped —
-  // overflow blocks wrap around with atomic accumulation
+  // overflow blocks wrap around with atomic accumulation.  The cap is what
+  // the zero-fill writes and bn_finalize_kernel reads (one lane per row, a
+  // cache line per load) on every call: at 8192 rows and C = 512 that was
+  // 33.5 MB; the atomics are a negligible volume either way.
   const int nblocks = std::min(
-      8192,
+      2048,
       2 * (int)(((Kout <= 64 ? (Kout + 63) / 64 : grid.x)) * grid.y));
   g16::ConvMeta cm{H, W, cl, S, R, (int)stride, (int)pad, HO, WO};
   NtExtras ex{};
@@ -1067,12 +1075,19 @@ std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
 // kernel's coalesced store phase (bit-identical to separate add_ / relu_bwd
 // passes); elsewhere the addend uses the NT kernel's EXTRAS epilogue and
 // out_mask a relu_bwd pass over the result.
-torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
-                                int64_t stride, int64_t pad, int64_t H,
-                                int64_t W,
-                                c10::optional<torch::Tensor> addend,
-                                c10::optional<torch::Tensor> addend_mask,
-                                c10::optional<torch::Tensor> out_mask) {
+// bns (optional; needs out_mask, excludes addend): ask the glds route for the
+// BN-backward sums of the masked dx as well; bns->ws stays undefined when
+// another route ran, which returns the same masked dx and no sums.
+struct DgradBnStats {
+  torch::Tensor bn_x, mean, rstd;
+  torch::Tensor ws;  // out
+};
+
+static torch::Tensor conv2d_dgrad_bf16_impl(
+    torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
+    int64_t W, c10::optional<torch::Tensor> addend,
+    c10::optional<torch::Tensor> addend_mask,
+    c10::optional<torch::Tensor> out_mask, DgradBnStats* bns) {
   int N = (int)dy.size(0), HOs = (int)dy.size(1), WOs = (int)dy.size(2),
       Kout = (int)dy.size(3);
   int Cin = (int)wr.size(0), R = (int)wr.size(1), S = (int)wr.size(2);
@@ -1115,6 +1130,12 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
   if (glds_epi_ok && ((int)stride & ((int)stride - 1)) == 0 &&
       ((int)stride == 1 || glds_s2)) {
     const int lgSt = log2_exact((int)stride);
+    if (lgSt >= 0 && bns) {
+      bns->ws = conv2d_dgrad_glds_bnstats(dy, wr, dx, zp, dpad, lgSt,
+                                          *out_mask, bns->bn_x, bns->mean,
+                                          bns->rstd);
+      if (bns->ws.defined()) return dx;
+    }
     if (lgSt >= 0 && conv2d_fwd_glds_ex(dy, wr, dx, zp, 1, dpad, nullptr, 0,
                                         lgSt, addend, out_mask))
       return dx;
@@ -1139,6 +1160,30 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
                                                M, Cin, K, 0, 0, 0, cm, ex);
   });
   return masked(dx);
+}
+
+torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
+                                int64_t stride, int64_t pad, int64_t H,
+                                int64_t W,
+                                c10::optional<torch::Tensor> addend,
+                                c10::optional<torch::Tensor> addend_mask,
+                                c10::optional<torch::Tensor> out_mask) {
+  return conv2d_dgrad_bf16_impl(dy, wr, stride, pad, H, W, addend, addend_mask,
+                                out_mask, nullptr);
+}
+
+// dx = relu_bwd(dgrad, out_mask) plus, when the glds kernel took the call,
+// the BN-backward sums workspace of the BN whose ReLU output is out_mask and
+// whose input is bn_x (conv_glds.hip, EPI_BNSTATS).  Returns {dx} or {dx, ws}.
+std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
+    torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
+    int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
+    torch::Tensor bn_mean, torch::Tensor bn_rstd) {
+  DgradBnStats bns{bn_x, bn_mean, bn_rstd, torch::Tensor()};
+  auto dx = conv2d_dgrad_bf16_impl(dy, wr, stride, pad, H, W, c10::nullopt,
+                                   c10::nullopt, out_mask, &bns);
+  if (bns.ws.defined()) return {dx, bns.ws};
+  return {dx};
 }
 
 // C[I,J] = A[...,M,I]^T @ B[...,M,J] summed over batch? No — per batch.

@@ -333,13 +333,14 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ ws,
 }
 
 // ---- BN bwd pass 2: dx (vectorized 8-channel slots) ----
-template <typename T, bool RELU>
+// G: gamma's type (fp32 master parameters next to 16-bit activations).
+template <typename T, bool RELU, typename G = T>
 __global__ void bn_bwd_dx_kernel(const T* __restrict__ dy,
                                  const T* __restrict__ x,
                                  const T* __restrict__ y, T* __restrict__ dx,
                                  const float* __restrict__ mean,
                                  const float* __restrict__ rstd,
-                                 const T* __restrict__ gamma,
+                                 const G* __restrict__ gamma,
                                  const float* __restrict__ dgamma,
                                  const float* __restrict__ dbeta, long long M,
                                  int C) {
@@ -746,6 +747,70 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor x,
                          mean.data_ptr<float>(), rstd.data_ptr<float>(), gp,
                          dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M,
                          C);
+  });
+  return {dx, dgamma_out, dbeta_out};
+}
+
+// BN backward whose stats pass already ran elsewhere: ws ([2R][C] fp32, rows
+// [0,R) partial sums of dy*xhat, rows [R,2R) of dy — the layout
+// bn_bwd_stats_kernel writes) comes from the conv dgrad that produced dy
+// (conv2d_dgrad_bnstats), and dy already carries the BN's ReLU mask.  Runs
+// the finalize and the two-tensor dx pass only.
+std::vector<torch::Tensor> bn_bwd_ws(torch::Tensor dy, torch::Tensor x,
+                                     torch::Tensor gamma, torch::Tensor mean,
+                                     torch::Tensor rstd, torch::Tensor ws) {
+  long long M = x.size(0);
+  int C = (int)x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= 2048,
+              "bn kernels need C % 8 == 0 and C <= 2048 (got ", C, ")");
+  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous() &&
+                  dy.numel() == x.numel() &&
+                  dy.scalar_type() == x.scalar_type(),
+              "bn_bwd_ws: dy and x must be contiguous and alike");
+  TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() && ws.dim() == 2 &&
+                  ws.scalar_type() == torch::kFloat32 && ws.size(1) == C &&
+                  ws.size(0) % 2 == 0 && ws.size(0) >= 2,
+              "bn_bwd_ws: ws must be fp32 [2R][C]");
+  TORCH_CHECK(gamma.is_contiguous() && gamma.numel() == C &&
+                  (gamma.scalar_type() == x.scalar_type() ||
+                   gamma.scalar_type() == torch::kFloat32),
+              "bn_bwd_ws: gamma must be [C], of x's dtype or fp32");
+  const int nrows = (int)(ws.size(0) / 2);
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto dgamma = torch::empty({C}, f32);
+  auto dbeta = torch::empty({C}, f32);
+  auto dx = torch::empty_like(dy);
+  auto stream = c10::hip::getCurrentHIPStream();
+  const bool wide = gamma.scalar_type() == torch::kFloat32;
+  auto dgamma_out =
+      wide ? dgamma : torch::empty({C}, x.options().dtype(gamma.scalar_type()));
+  auto dbeta_out =
+      wide ? dbeta : torch::empty({C}, x.options().dtype(gamma.scalar_type()));
+  DDP_DISPATCH_FLOAT(x.scalar_type(), "bn_bwd_ws", [&] {
+    const auto* dyp = reinterpret_cast<const scalar_t*>(dy.data_ptr());
+    const auto* xp = reinterpret_cast<const scalar_t*>(x.data_ptr());
+    hipLaunchKernelGGL((nrm::bn_bwd_finalize_kernel<scalar_t>), dim3(C),
+                       dim3(256), 0, stream, ws.data_ptr<float>(), nrows,
+                       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
+                       wide ? nullptr
+                            : reinterpret_cast<scalar_t*>(dgamma_out.data_ptr()),
+                       wide ? nullptr
+                            : reinterpret_cast<scalar_t*>(dbeta_out.data_ptr()),
+                       C);
+    auto launch_dx = [&](const auto* gp) {
+      using G = std::remove_cv_t<std::remove_pointer_t<decltype(gp)>>;
+      hipLaunchKernelGGL((nrm::bn_bwd_dx_kernel<scalar_t, false, G>),
+                         dim3(grid_1d(M * C / 8, 256)), dim3(256), 0, stream,
+                         dyp, xp, static_cast<const scalar_t*>(nullptr),
+                         reinterpret_cast<scalar_t*>(dx.data_ptr()),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(), gp,
+                         dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), M,
+                         C);
+    };
+    if (wide)
+      launch_dx(gamma.data_ptr<float>());
+    else
+      launch_dx(reinterpret_cast<const scalar_t*>(gamma.data_ptr()));
   });
   return {dx, dgamma_out, dbeta_out};
 }

@@ -54,6 +54,10 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
 std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
     torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
     int64_t stride, int64_t pad, bool relu);
+std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
+    torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
+    int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
+    torch::Tensor bn_mean, torch::Tensor bn_rstd);
 // gemm_f32.hip
 torch::Tensor bmm_nt_f32(torch::Tensor A, torch::Tensor B,
                          c10::optional<torch::Tensor> bias, bool relu);
@@ -83,6 +87,9 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor gamma, torch::Tensor mean,
                                   torch::Tensor rstd,
                                   c10::optional<torch::Tensor> y_relu);
+std::vector<torch::Tensor> bn_bwd_ws(torch::Tensor dy, torch::Tensor x,
+                                     torch::Tensor gamma, torch::Tensor mean,
+                                     torch::Tensor rstd, torch::Tensor ws);
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor gamma,
                                          torch::Tensor beta, double eps);
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
@@ -256,6 +263,28 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
   return dx;
 }
 
+// conv2d_dgrad(..., out_mask=out_mask) that, when the glds kernel takes the
+// call, also returns the BN-backward sums workspace of the BN with input
+// bn_x, saved bn_mean / bn_rstd and ReLU output out_mask (for bn_bwd_ws).
+// Every other route returns the same masked dx and None.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv2d_dgrad_bnstats(
+    torch::Tensor dy, torch::Tensor w, int64_t stride, int64_t pad, int64_t H,
+    int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
+    torch::Tensor bn_mean, torch::Tensor bn_rstd) {
+  int R = (int)w.size(1), S = (int)w.size(2);
+  TORCH_CHECK(pad <= R - 1 && pad <= S - 1, "dgrad needs pad <= kernel-1");
+  if (is_bf16(dy) && pow2_ge((int)dy.size(3), 8)) {
+    auto wr = weight_rot(w.contiguous());  // [C, R, S, Kout]
+    auto r = conv2d_dgrad_bnstats_bf16(dy.contiguous(), wr, stride, pad, H, W,
+                                       out_mask, bn_x, bn_mean, bn_rstd);
+    if (r.size() == 2) return {r[0], r[1]};
+    return {r[0], c10::nullopt};
+  }
+  return {conv2d_dgrad(dy, w, stride, pad, H, W, c10::nullopt, c10::nullopt,
+                       out_mask),
+          c10::nullopt};
+}
+
 torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
                            int64_t pad, int64_t R, int64_t S) {
   int Cin = (int)x.size(3);
@@ -303,6 +332,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("addend") = c10::nullopt,
         py::arg("addend_mask") = c10::nullopt,
         py::arg("out_mask") = c10::nullopt);
+  m.def("conv2d_dgrad_bnstats", &conv2d_dgrad_bnstats, py::arg("dy"),
+        py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("H"),
+        py::arg("W"), py::arg("out_mask"), py::arg("bn_x"),
+        py::arg("bn_mean"), py::arg("bn_rstd"));
   m.def("conv2d_fwd_stats", &conv2d_fwd_stats_bf16, py::arg("x"),
         py::arg("w"), py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
         py::arg("pad") = 0, py::arg("relu") = false);
@@ -326,6 +359,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_infer", &bn_infer);
   m.def("bn_bwd", &bn_bwd, py::arg("dy"), py::arg("x"), py::arg("gamma"),
         py::arg("mean"), py::arg("rstd"), py::arg("y_relu") = c10::nullopt);
+  m.def("bn_bwd_ws", &bn_bwd_ws, py::arg("dy"), py::arg("x"),
+        py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("ws"));
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("softmax_fwd", &softmax_fwd);

@@ -18,7 +18,16 @@ Why (measured on MI355X, ResNet-18/CIFAR bf16 step profile):
   layout.  The dgrads now run on the glds conv kernel, whose epilogue
   already stages the tile through LDS and stores coalesced 16-B row chunks;
   addend and mask are read with that same pattern, after the accumulator is
-  rounded to bf16, so the result is bit-identical to the separate passes.
+  rounded to bf16, so the result is bit-identical to the separate passes;
+* the backward mirror of the forward stats epilogue (``PDT_DGRAD_BNSTATS``,
+  below): the dgrad that produces ``dz`` for an in-block BN with a ReLU
+  (``bn1`` of a BasicBlock, ``bn1``/``bn2`` of a Bottleneck) applies that
+  ReLU's mask in its store phase and accumulates the BN's backward sums
+  (sum dz, sum dz*xhat per channel) there (``conv2d_dgrad_bnstats``).  The
+  BN backward then runs only its finalize and a two-tensor dx pass
+  (``bn_bwd_ws``): the three-tensor stats pass disappears and the dx pass no
+  longer reads the ReLU output.  Where the glds kernel declines the shape no
+  workspace comes back and ``bn_bwd`` runs on the already-masked ``dz``.
 
 ReLU-mask handshake between adjacent blocks (``PDT_DGRAD_EPILOGUE``, below):
 a block's output is ``relu(·)``, and its backward starts by masking ``dy``
@@ -72,6 +81,36 @@ def _use_dgrad_epilogue():
     return os.environ.get("PDT_DGRAD_EPILOGUE", "1") != "0"
 
 
+def _use_dgrad_bnstats():
+    # BN-backward sums from the dgrad store phase (module docstring);
+    # PDT_DGRAD_BNSTATS=0 restores the separate bn_bwd stats pass (A/B runs).
+    # Read once per block forward; the backward follows it.
+    return os.environ.get("PDT_DGRAD_BNSTATS", "1") != "0"
+
+
+def _dgrad_for_bn_relu(ext, bns, dy, w, stride, pad, H, W, t, z, mean, rstd):
+    """dgrad of ``dy`` through the conv with weight ``w`` whose input was the
+    output ``z`` of a BN+ReLU with BN input ``t``.  Returns (dz, ws, masked):
+    with ``bns`` dz carries the ReLU mask, and ws the BN-backward sums when
+    the glds kernel ran (else None)."""
+    if not bns:
+        return ext.conv2d_dgrad(dy, w, stride, pad, H, W), None, False
+    dz, ws = ext.conv2d_dgrad_bnstats(dy, w, stride, pad, H, W, z, t, mean,
+                                      rstd)
+    return dz, ws, True
+
+
+def _bn_relu_bwd(ext, dz, ws, masked, t, z, gamma, mean, rstd):
+    """Backward of that BN+ReLU from what ``_dgrad_for_bn_relu`` returned."""
+    if ws is not None:
+        dt, dg, db = ext.bn_bwd_ws(_flat(dz), _flat(t), gamma, mean, rstd, ws)
+    else:
+        # masked without sums: another dgrad route ran and applied the mask
+        dt, dg, db = ext.bn_bwd(_flat(dz), _flat(t), gamma, mean, rstd,
+                                None if masked else _flat(z))
+    return dt.reshape(t.shape), dg, db
+
+
 def _accept_premask(x, accept, epi):
     """Consumer side of the handshake: True when this block will mask its
     returned dx by ``x > 0`` and has told x's producer so."""
@@ -102,11 +141,11 @@ class _FusedBasicBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(
         ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, bn1, bn2, bnd, stride,
-        offer=False, mask_in=False, epi=False,
+        offer=False, mask_in=False, epi=False, bns=False,
     ):
         ext = native()
         # handshake state (module docstring): None = no offer made
-        ctx.epi, ctx.mask_in = epi, mask_in
+        ctx.epi, ctx.mask_in, ctx.bns = epi, mask_in, bns
         ctx.dy_premasked = False if (offer and epi) else None
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
@@ -166,14 +205,13 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             with torch.cuda.stream(side):
                 dw2 = ext.conv2d_wgrad(dx2, z, 1, 1, 3, 3).to(w2.dtype)
         # conv2 backward dgrad stays on the critical path
-        dz = ext.conv2d_dgrad(dx2, w2, 1, 1, Hz, Wz)
+        dz, ws1, masked = _dgrad_for_bn_relu(
+            ext, ctx.bns, dx2, w2, 1, 1, Hz, Wz, t1, z, mean1, rstd1)
         if not use_side:
             dw2 = ext.conv2d_wgrad(dx2, z, 1, 1, 3, 3).to(w2.dtype)
         # bn1 backward (its own fused ReLU: z is bn1's relu output)
-        dt1, dg1, db1 = ext.bn_bwd(
-            _flat(dz), _flat(t1), g1, mean1, rstd1, _flat(z)
-        )
-        dt1 = dt1.reshape(t1.shape)
+        dt1, dg1, db1 = _bn_relu_bwd(ext, dz, ws1, masked, t1, z, g1, mean1,
+                                     rstd1)
         if use_side:
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -202,7 +240,7 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             for t in (dw2, dw1) + ((dwd,) if wd is not None else ()):
                 t.record_stream(main)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride,
@@ -213,13 +251,14 @@ def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride,
     adjacent wired block (ReLU-mask handshake, module docstring)."""
     epi = _use_dgrad_epilogue()
     mask_in = _accept_premask(x, accept, epi)
+    bns = _use_dgrad_bnstats()
     return _FusedBasicBlockFn.apply(
         x, conv1.weight, bn1.weight, bn1.bias,
         conv2.weight, bn2.weight, bn2.bias,
         convd.weight if convd is not None else None,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
-        bn1, bn2, bnd, stride, offer, mask_in, epi,
+        bn1, bn2, bnd, stride, offer, mask_in, epi, bns,
     )
 
 
@@ -230,9 +269,9 @@ class _FusedBottleneckFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd,
                 bn1, bn2, bn3, bnd, stride,
-                offer=False, mask_in=False, epi=False):
+                offer=False, mask_in=False, epi=False, bns=False):
         ext = native()
-        ctx.epi, ctx.mask_in = epi, mask_in
+        ctx.epi, ctx.mask_in, ctx.bns = epi, mask_in, bns
         ctx.dy_premasked = False if (offer and epi) else None
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
@@ -283,18 +322,18 @@ class _FusedBottleneckFn(torch.autograd.Function):
         g2d = _flat(g)
         dx3, dg3, db3 = ext.bn_bwd(g2d, _flat(t3), g3, mean3, rstd3, None)
         dx3 = dx3.reshape(t3.shape)
-        dz2 = ext.conv2d_dgrad(dx3, w3, 1, 0, H2, W2)
+        dz2, ws2, masked = _dgrad_for_bn_relu(
+            ext, ctx.bns, dx3, w3, 1, 0, H2, W2, t2, z2, mean2, rstd2)
         dw3 = ext.conv2d_wgrad(dx3, z2, 1, 0, 1, 1).to(w3.dtype)
 
-        dt2, dg2, db2 = ext.bn_bwd(
-            _flat(dz2), _flat(t2), g2, mean2, rstd2, _flat(z2))
-        dt2 = dt2.reshape(t2.shape)
-        dz1 = ext.conv2d_dgrad(dt2, w2, stride, 1, H1, W1)
+        dt2, dg2, db2 = _bn_relu_bwd(ext, dz2, ws2, masked, t2, z2, g2, mean2,
+                                     rstd2)
+        dz1, ws1, masked = _dgrad_for_bn_relu(
+            ext, ctx.bns, dt2, w2, stride, 1, H1, W1, t1, z1, mean1, rstd1)
         dw2 = ext.conv2d_wgrad(dt2, z1, stride, 1, 3, 3).to(w2.dtype)
 
-        dt1, dg1, db1 = ext.bn_bwd(
-            _flat(dz1), _flat(t1), g1, mean1, rstd1, _flat(z1))
-        dt1 = dt1.reshape(t1.shape)
+        dt1, dg1, db1 = _bn_relu_bwd(ext, dz1, ws1, masked, t1, z1, g1, mean1,
+                                     rstd1)
         dw1 = ext.conv2d_wgrad(dt1, x, 1, 0, 1, 1).to(w1.dtype)
 
         if wd is None:
@@ -308,13 +347,14 @@ class _FusedBottleneckFn(torch.autograd.Function):
             dx = _skip_grad_dgrad(ext, ctx, dtd, wd, stride, 0, H, W, dxa, x)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3,
                 dwd, dgd, dbd, None, None, None, None, None,
-                None, None, None)
+                None, None, None, None)
 
 
 def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
                      stride, offer=False, accept=False):
     epi = _use_dgrad_epilogue()
     mask_in = _accept_premask(x, accept, epi)
+    bns = _use_dgrad_bnstats()
     return _FusedBottleneckFn.apply(
         x, conv1.weight, bn1.weight, bn1.bias,
         conv2.weight, bn2.weight, bn2.bias,
@@ -322,5 +362,5 @@ def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
         convd.weight if convd is not None else None,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
-        bn1, bn2, bn3, bnd, stride, offer, mask_in, epi,
+        bn1, bn2, bn3, bnd, stride, offer, mask_in, epi, bns,
     )
