@@ -26,6 +26,17 @@
 // run two blocks per CU (better glds latency hiding).
 // Covers every non-stem ResNet-18/CIFAR conv (fwd and, via the rotated-
 // weight identity, stride-1 dgrad).  Reference scope: SURVEY §2b conv row.
+//
+// Halo-resident A (template parameter HW, 64-wide tile only): the per-tap
+// gather above re-reads every input element once per tap, and the engine is
+// bound by that cache-to-LDS fill, not by MFMA or HBM (profiles/
+// r06_conv_halo64.md).  For 3x3 stride-1 pad-1 convs with C = 64 whose M-tile
+// is whole rows of one image (W = 16, 32 or 64; conv_halo64_eligible) the
+// block stages its (256/W + 2) x (W + 2) input patch once, and the K-loop
+// streams only the 8-KB weight tile of each tap; same K order, same MFMA
+// sequence per output element, every epilogue shared, so results are
+// bit-identical to the per-tap route.  PDT_CONV_HALO64=0 (read per call)
+// restores the per-tap route for A/B runs.
 
 #include <torch/extension.h>
 
@@ -71,8 +82,27 @@ constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_MASK = 2, EPI_ADD_MASK = 3;
 // with row = block id % R: the [2R][C] layout of bn_bwd_stats_kernel.
 constexpr int EPI_BNSTATS = 4, EPI_MASK_BNSTATS = EPI_MASK | EPI_BNSTATS;
 
-template <int BN, bool STATS, int EPI = EPI_NONE>
-__global__ __launch_bounds__(THREADS, BN == 64 ? 2 : 1)
+// Halo-resident A operand (HW != 0; 64-wide tile, 3x3 stride-1 pad-1, C = 64,
+// image width HW): a 256-row M-tile is BM/HW whole rows of one image, so its
+// input patch — those rows plus one above, one below and a column each side —
+// is staged ONCE and all nine taps read it, instead of re-gathering the tile
+// per tap.  Halo rows are HP positions apart (HW + 2 rounded up to 8); a
+// 1-KiB piece is 8 positions stored chunk-major, [16-B chunk][position & 7],
+// by swapping the roles of lane>>3 and lane&7 in the glds SOURCE address.
+// The 16 rows of an A fragment are 16 consecutive positions, so every
+// ds_read_b128 lane group covers 8 consecutive positions of an even chunk and
+// 8 of an odd one: all 16 slots of the 256-B bank row, conflict-free for any
+// tap shift.  A tap (r, s) is then the per-lane address of column shift s
+// plus the constant (r * HP + ...) * 128 — no address arithmetic in the loop.
+constexpr int halo_pitch(int hw) { return (hw + 2 + 7) & ~7; }
+constexpr int halo_bytes(int hw) {
+  return hw ? (BM / hw + 2) * halo_pitch(hw) * BK * 2 : 0;
+}
+
+// (the second launch bound is waves per SIMD: the halo variant asks for the 4
+// that two co-resident blocks need, i.e. at most 128 VGPRs)
+template <int BN, bool STATS, int EPI = EPI_NONE, int HW = 0>
+__global__ __launch_bounds__(THREADS, HW ? 4 : BN == 64 ? 2 : 1)
 void conv_fwd_glds_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, const __hip_bfloat16* __restrict__ zpad,
@@ -85,7 +115,11 @@ void conv_fwd_glds_kernel(
                 "dgrad epilogues carry no forward stats");
   static_assert(!(EPI & EPI_BNSTATS) || EPI == EPI_MASK_BNSTATS,
                 "BN-backward sums ride only with the mask, without an addend");
-  __shared__ __hip_bfloat16 smem[2 * (BM + BN) * BK];
+  static_assert(HW == 0 || (BN == 64 && BM % HW == 0 && HW % 16 == 0),
+                "halo variant: 64-wide tile, whole image rows per M-tile");
+  constexpr int HALO_ELEMS = halo_bytes(HW) / 2;
+  __shared__ __hip_bfloat16
+      smem[HW ? HALO_ELEMS + 2 * BN * BK : 2 * (BM + BN) * BK];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -183,41 +217,134 @@ void conv_fwd_glds_kernel(
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int NT = K / BK;
-  stage(0, 0);
-  __syncthreads();
+  if constexpr (HW == 0) {
+    const int NT = K / BK;
+    stage(0, 0);
+    __syncthreads();
 
-  int cur = 0;
-  for (int kt = 0; kt < NT; ++kt) {
-    if (kt + 1 < NT) stage(cur ^ 1, kt + 1);
-    const __hip_bfloat16* sa = smem + cur * ((BM + BN) * BK);
-    const __hip_bfloat16* sb = sa + BM * BK;
-    bf16x8 bf[NI][2];
+    int cur = 0;
+    for (int kt = 0; kt < NT; ++kt) {
+      if (kt + 1 < NT) stage(cur ^ 1, kt + 1);
+      const __hip_bfloat16* sa = smem + cur * ((BM + BN) * BK);
+      const __hip_bfloat16* sb = sa + BM * BK;
+      bf16x8 bf[NI][2];
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
+      for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int row = wn + ni * 16 + frow;
-        bf[ni][ks] = *(const bf16x8*)((const char*)(sb + row * BK) +
-                                      kswz(row, ks * 64 + fkb));
+        for (int ks = 0; ks < 2; ++ks) {
+          const int row = wn + ni * 16 + frow;
+          bf[ni][ks] = *(const bf16x8*)((const char*)(sb + row * BK) +
+                                        kswz(row, ks * 64 + fkb));
+        }
+#pragma unroll
+      for (int mi = 0; mi < 8; ++mi) {
+        bf16x8 af[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int row = wm + mi * 16 + frow;
+          af[ks] = *(const bf16x8*)((const char*)(sa + row * BK) +
+                                    kswz(row, ks * 64 + fkb));
+        }
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][ni] = mfma16(af[0], bf[ni][0], acc[mi][ni]);
+          acc[mi][ni] = mfma16(af[1], bf[ni][1], acc[mi][ni]);
+        }
       }
+      __syncthreads();
+      cur ^= 1;
+    }
+  } else {
+    // ---- halo-resident A: stage the patch once, stream only the weights
+    constexpr int HP = halo_pitch(HW);
+    constexpr int KR = BM / HW;                 // image rows per M-tile
+    constexpr int PPR = HP / 8;                 // 1-KiB pieces per halo row
+    constexpr int NPIECE = (KR + 2) * PPR;
+    __hip_bfloat16* sw = smem + HALO_ELEMS;     // two weight tiles
+    const int tpi = g.H / KR;                   // M-tiles per image
+    const int tile = (int)(m0 / BM);            // host: M / BM fits an int
+    const long long img = tile / tpi;
+    const int h0 = (tile - (int)img * tpi) * KR;
+
+    auto stage_w = [&](int buf, int kt) {
+      __hip_bfloat16* sb = sw + buf * (BN * BK);
 #pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      bf16x8 af[2];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int row = wm + mi * 16 + frow;
-        af[ks] = *(const bf16x8*)((const char*)(sa + row * BK) +
-                                  kswz(row, ks * 64 + fkb));
+      for (int r = 0; r < RB; ++r) {
+        const int row = r * 64 + wave * 8 + srow;
+        const long long kk = (long long)kt * BK + kswz(row, schunk * 16) / 2;
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) unsigned int*)(
+                w + (long long)(n0 + row) * K + kk),
+            (__attribute__((address_space(3))) unsigned int*)(
+                sb + (r * 64 + wave * 8) * BK),
+            16, 0, 0);
       }
+    };
+    stage_w(0, 0);
+    // piece pc = 8 positions of halo row pc / PPR; lane: position lane & 7,
+    // chunk lane >> 3.  Rows outside the image, the two border columns and
+    // the pitch padding come from the zero page.
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        acc[mi][ni] = mfma16(af[0], bf[ni][0], acc[mi][ni]);
-        acc[mi][ni] = mfma16(af[1], bf[ni][1], acc[mi][ni]);
+    for (int p0 = 0; p0 < NPIECE; p0 += 8) {
+      const int pc = p0 + wave;
+      if (pc < NPIECE) {
+        const int hr = pc / PPR;
+        const int hi = h0 - 1 + hr;
+        const int wi = (pc - hr * PPR) * 8 + (lane & 7) - 1;
+        const __hip_bfloat16* src = zpad;
+        if ((unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)HW)
+          src = x + (((img * g.H + hi) * HW + wi) << 6) + (lane >> 3) * 8;
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) unsigned int*)src,
+            (__attribute__((address_space(3))) unsigned int*)(smem + pc * 512),
+            16, 0, 0);
       }
     }
+    // per-lane fragment address for each column shift s of a tap
+    int abase[3];
+#pragma unroll
+    for (int st = 0; st < 3; ++st) {
+      const int q = frow + st;
+      abase[st] = (wm / HW) * HP * 128 + (q >> 3) * 1024 + (q & 7) * 16 +
+                  (lane >> 4) * 128;
+    }
     __syncthreads();
-    cur ^= 1;
+
+    // tap-major K, one tap per 64-deep step: a real loop over the tap rows
+    // (fully unrolled, the dgrad epilogue modes spill), the three column
+    // shifts unrolled so that their offsets stay immediates
+#pragma unroll 1
+    for (int rt = 0; rt < 3; ++rt)
+#pragma unroll
+    for (int st = 0; st < 3; ++st) {
+      const int kt = rt * 3 + st;
+      if (kt + 1 < 9) stage_w((kt + 1) & 1, kt + 1);
+      const __hip_bfloat16* sb = sw + (kt & 1) * (BN * BK);
+      const char* ha = (const char*)smem + rt * (HP * 128) + abase[st];
+      bf16x8 bf[NI][2];
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int row = wn + ni * 16 + frow;
+          bf[ni][ks] = *(const bf16x8*)((const char*)(sb + row * BK) +
+                                        kswz(row, ks * 64 + fkb));
+        }
+#pragma unroll
+      for (int mi = 0; mi < 8; ++mi) {
+        const int cpos = ((mi * 16) / HW) * HP + (mi * 16) % HW;
+        bf16x8 af[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+          af[ks] = *(const bf16x8*)(ha + cpos * 128 + ks * 512);
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][ni] = mfma16(af[0], bf[ni][0], acc[mi][ni]);
+          acc[mi][ni] = mfma16(af[1], bf[ni][1], acc[mi][ni]);
+        }
+      }
+      __syncthreads();
+    }
   }
 
   // ---- BN-stats partials (before the bf16 staging): per column, sum and
@@ -407,6 +534,22 @@ struct GldsBnStats {
 // has today; blocks beyond that wrap (every block adds with atomics).
 constexpr int kBnStatsRows = 1024;
 
+// Shape test of the halo-resident A route (cg::conv_fwd_glds_kernel, HW != 0);
+// H, W are the input's, which pad 1 / stride 1 make the output's as well.
+// Pure host arithmetic — the launcher calls it, and it is exported so that a
+// test can tell which route a shape takes.  The LDS budget is the 64-wide
+// tile's 80 KB (two blocks per CU): it admits W = 16, 32 and 64.
+bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
+                          int64_t R, int64_t S, int64_t stride, int64_t pad) {
+  if (R != 3 || S != 3 || stride != 1 || pad != 1 || C != 64) return false;
+  if (Kout <= 0 || Kout % 64 || Kout % 128 == 0) return false;  // BN == 64
+  if (W < 16 || W % 16 || cg::BM % W) return false;
+  const int64_t k = cg::BM / W;  // image rows per 256-row M-tile
+  if (k > H || H % k) return false;
+  return cg::halo_bytes((int)W) + 2 * 64 * cg::BK * 2 <=
+         2 * (cg::BM + 64) * cg::BK * 2;
+}
+
 // Host entry: returns true when handled.  y must be pre-allocated
 // [N,HO,WO,Kout]; stats_ws (optional) pre-zeroed [2*ws_nblocks, Kout].
 // addend / out_mask (optional, dgrad only, never with stats_ws): y-shaped
@@ -475,8 +618,18 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
     meanp = bns->mean.data_ptr<float>();
     rstdp = bns->rstd.data_ptr<float>();
   }
+  // halo-resident A for the 64-channel 3x3 layers; PDT_CONV_HALO64=0 keeps
+  // the per-tap gather (read per call, so one process can run both routes)
+  const char* eh = getenv("PDT_CONV_HALO64");
+  const bool halo = !(eh && eh[0] == '0') && lgSt == 0 && H == HO && W == WO &&
+                    conv_halo64_eligible(H, W, C, Kout, R, S, stride, pad);
+#define CG_HALO(ST, EP)                                       \
+  (W == 16   ? &cg::conv_fwd_glds_kernel<64, ST, EP, 16>      \
+   : W == 32 ? &cg::conv_fwd_glds_kernel<64, ST, EP, 32>      \
+             : &cg::conv_fwd_glds_kernel<64, ST, EP, 64>)
 #define CG_KERN(ST, EP)                                       \
-  (BN == 256   ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
+  (halo        ? CG_HALO(ST, EP)                              \
+   : BN == 256 ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
    : BN == 128 ? &cg::conv_fwd_glds_kernel<128, ST, EP>       \
                : &cg::conv_fwd_glds_kernel<64, ST, EP>)
   auto kern = bns                     ? CG_KERN(false, cg::EPI_MASK_BNSTATS)
@@ -486,6 +639,7 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
               : epi == cg::EPI_MASK   ? CG_KERN(false, cg::EPI_MASK)
                                       : CG_KERN(false, cg::EPI_ADD_MASK);
 #undef CG_KERN
+#undef CG_HALO
   hipLaunchKernelGGL(kern, grid, dim3(cg::THREADS), 0, stream, ptr16<bf16>(x),
                      ptr16<bf16>(w), ptr16<bf16>(y), ptr16<bf16>(zp), (int)M,
                      Kout, K, g, stats_ws, ws_nblocks, addp, maskp, meanp,

@@ -15,6 +15,12 @@
 // (a multiple of 64 banks for C>=32), so the 8-halfword c-chunks are
 // XOR-swizzled by the halo position (chunk' = chunk ^ (pos & (chunks-1)))
 // in both the staging writes and the fragment reads.
+//
+// The glds engine (conv_glds.hip) takes the shapes it covers first.  Its
+// 64-wide tile has the same once-per-block patch staging for C = 64 (template
+// parameter HW there: 8 waves, 16x16x32 MFMAs, BK = 64, a conflict-free
+// chunk-major patch layout); this 4-wave kernel remains the route for what
+// the glds engine declines.
 
 #include <torch/extension.h>
 

@@ -58,6 +58,9 @@ std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
     torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
     int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
     torch::Tensor bn_mean, torch::Tensor bn_rstd);
+// conv_glds.hip: does a conv shape take the halo-resident 64-wide tile
+bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
+                          int64_t R, int64_t S, int64_t stride, int64_t pad);
 // gemm_f32.hip
 torch::Tensor bmm_nt_f32(torch::Tensor A, torch::Tensor B,
                          c10::optional<torch::Tensor> bias, bool relu);
@@ -339,6 +342,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd_stats", &conv2d_fwd_stats_bf16, py::arg("x"),
         py::arg("w"), py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
         py::arg("pad") = 0, py::arg("relu") = false);
+  m.def("conv_halo64_eligible", &conv_halo64_eligible, py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("Kout"), py::arg("R"),
+        py::arg("S"), py::arg("stride"), py::arg("pad"));
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("relu_fwd", &relu_fwd);
   m.def("relu_bwd", &relu_bwd);
