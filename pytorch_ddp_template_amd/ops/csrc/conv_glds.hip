@@ -37,6 +37,17 @@
 // sequence per output element, every epilogue shared, so results are
 // bit-identical to the per-tap route.  PDT_CONV_HALO64=0 (read per call)
 // restores the per-tap route for A/B runs.
+//
+// Parity-split stride-2 dgrad (template parameter PAR, all three tile widths,
+// the five dgrad epilogue modes): a 3x3 stride-2 pad-1 dgrad run as a stride-1
+// conv over the zero-stuffed dy executes nine taps per dx pixel of which only
+// 1, 2, 2 or 4 (by pixel parity) carry data.  With PAR an M-tile holds pixels
+// of one parity class and the K-loop runs that class's taps only: a quarter of
+// the fills, LDS reads and MFMAs, same products in the same order, shared
+// epilogues with the row address mapped to (n, 2i + a, 2j + b); dx is
+// bit-identical to the stuffed route (profiles/r07_dgrad_s2_parity.md).
+// conv_dgrad_s2_parity_eligible is the gate; PDT_DGRAD_S2_PARITY=0 (read per
+// call) restores the stuffed route for A/B runs.
 
 #include <torch/extension.h>
 
@@ -99,9 +110,26 @@ constexpr int halo_bytes(int hw) {
   return hw ? (BM / hw + 2) * halo_pitch(hw) * BK * 2 : 0;
 }
 
+// Parity-split stride-2 dgrad (PAR; 3x3 stride-2 pad-1, dy dims H x W powers
+// of two, dx = 2H x 2W): the stuffed gather above runs all nine taps over every
+// dx pixel although a pixel of parity class (a, b) = (h & 1, w & 1) has only
+// (1 + a) * (1 + b) taps on the stride grid.  Here an M-tile is 256
+// consecutive dy positions (n, i, j) of ONE class, its rows are the dx pixels
+// (n, 2i + a, 2j + b), and the K-loop runs the class's taps only.  With the
+// rotated weight and dpad = 1 the stuffed source row of tap rt is h - 1 + rt:
+//   even h = 2i     : rt = 1 only             -> dy row i
+//   odd  h = 2i + 1 : rt = 0 -> dy row i,  rt = 2 -> dy row i + 1
+// and the same for columns (st, j).  A source index equal to H or W (the last
+// odd row / column) reads the zero page.  Taps run in ascending (rt, st)
+// order with today's weight tile addresses, so every dx element sums the same
+// nonzero products in the same order as on the stuffed route, which only adds
+// exact zeros in between.  The class is the low two bits of the remapped tile
+// index, so every XCD gets the same mix of 1-, 2- and 4-tap tiles and the
+// four classes of one position tile read the same dy rows through one L2.
+//
 // (the second launch bound is waves per SIMD: the halo variant asks for the 4
 // that two co-resident blocks need, i.e. at most 128 VGPRs)
-template <int BN, bool STATS, int EPI = EPI_NONE, int HW = 0>
+template <int BN, bool STATS, int EPI = EPI_NONE, int HW = 0, bool PAR = false>
 __global__ __launch_bounds__(THREADS, HW ? 4 : BN == 64 ? 2 : 1)
 void conv_fwd_glds_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
@@ -117,6 +145,8 @@ void conv_fwd_glds_kernel(
                 "BN-backward sums ride only with the mask, without an addend");
   static_assert(HW == 0 || (BN == 64 && BM % HW == 0 && HW % 16 == 0),
                 "halo variant: 64-wide tile, whole image rows per M-tile");
+  static_assert(!PAR || (!STATS && HW == 0),
+                "parity split: dgrad only, per-tap gather");
   constexpr int HALO_ELEMS = halo_bytes(HW) / 2;
   __shared__ __hip_bfloat16
       smem[HW ? HALO_ELEMS + 2 * BN * BK : 2 * (BM + BN) * BK];
@@ -134,7 +164,13 @@ void conv_fwd_glds_kernel(
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
   }
   const int n0 = (int)(bid % gridDim.x) * BN;
-  const long long m0 = (bid / gridDim.x) * BM;
+  const long long mtile = bid / gridDim.x;
+  // PAR: class (pa, pb) = (h & 1, w & 1) of the tile's dx pixels; m0 then
+  // counts dy positions
+  const int pa = PAR ? (int)(mtile >> 1) & 1 : 0;
+  const int pb = PAR ? (int)mtile & 1 : 0;
+  const long long m0 = (PAR ? mtile >> 2 : mtile) * BM;
+  const int lgH = PAR ? 31 - __clz(g.H) : 0, lgW = PAR ? 31 - __clz(g.W) : 0;
   const long long flat_id = bid;
 
   // ---- staging geometry (v1 pattern): per round 64 rows; wave w rows
@@ -154,6 +190,13 @@ void conv_fwd_glds_kernel(
     // hoisted out of the K-loop, so plain div/mod (non-pow2 spatial: the
     // ResNet-50 224-input pyramid is 56/28/14/7) costs nothing hot
     const long long m = m0 + r * 64 + wave * 8 + srow;
+    if constexpr (PAR) {
+      // pow2 dy dims: m IS the dy position of tap offset (0, 0)
+      hv[r] = (int)(m >> lgW) & (g.H - 1);
+      wv[r] = (int)m & (g.W - 1);
+      nbase[r] = m;
+      continue;
+    }
     const int wo = (int)(m % g.WO);
     const long long t = m / g.WO;
     const int ho = (int)(t % g.HO);
@@ -167,8 +210,16 @@ void conv_fwd_glds_kernel(
   auto stage = [&](int buf, int kt) {
     __hip_bfloat16* sa = smem + buf * ((BM + BN) * BK);
     __hip_bfloat16* sb = sa + BM * BK;
-    const int tap = (kt << 6) >> g.lgC;
+    int tap = (kt << 6) >> g.lgC;
     const int c0 = (kt << 6) & (g.C - 1);
+    // PAR: kt counts the class's taps only; its tap index is (dh, dw) in
+    // {0, 1}^2, the source offset, and (rt, st) = (pa ? 2 dh : 1, pb ? 2 dw : 1)
+    const int dh = pb ? tap >> 1 : tap, dw = pb ? tap & 1 : 0;
+    int wkt = kt;  // k-tile of the weight operand
+    if constexpr (PAR) {
+      tap = (pa ? 2 * dh : 1) * 3 + (pb ? 2 * dw : 1);
+      wkt = (tap << (g.lgC - 6)) + (c0 >> 6);
+    }
     const int rt = tap / g.S, st = tap - rt * g.S;
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
@@ -176,7 +227,10 @@ void conv_fwd_glds_kernel(
       const int kk = c0 + kswz(row, schunk * 16) / 2;
       const __hip_bfloat16* src = zpad;
       const int hs = hv[r] + rt, ws = wv[r] + st;
-      if ((unsigned)(hs >> g.lgSt) < (unsigned)g.H &&
+      if constexpr (PAR) {
+        if (hv[r] + dh < g.H && wv[r] + dw < g.W)
+          src = x + ((nbase[r] + dh * g.W + dw) << g.lgC) + kk;
+      } else if ((unsigned)(hs >> g.lgSt) < (unsigned)g.H &&
           (unsigned)(ws >> g.lgSt) < (unsigned)g.W &&
           ((hs | ws) & smask) == 0)
         src = x + ((nbase[r] + (long long)(hs >> g.lgSt) * g.W +
@@ -192,7 +246,7 @@ void conv_fwd_glds_kernel(
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
       const int row = r * 64 + wave * 8 + srow;
-      const long long kk = (long long)kt * BK + kswz(row, schunk * 16) / 2;
+      const long long kk = (long long)wkt * BK + kswz(row, schunk * 16) / 2;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
               w + (long long)(n0 + row) * K + kk),
@@ -218,7 +272,7 @@ void conv_fwd_glds_kernel(
     for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   if constexpr (HW == 0) {
-    const int NT = K / BK;
+    const int NT = PAR ? ((1 + pa) * (1 + pb)) << (g.lgC - 6) : K / BK;
     stage(0, 0);
     __syncthreads();
 
@@ -394,9 +448,21 @@ void conv_fwd_glds_kernel(
   constexpr int PF = 2;
   static_assert(NR >= PF, "epilogue prefetch deeper than the store loop");
   short8 av[PF] = {}, mv[PF] = {};
+  // y row of a tile row; PAR: dx pixel (n, 2i + pa, 2j + pb) of dy position
+  // m0 + row = (n, i, j)
+  auto yrow = [&](int row) -> long long {
+    if constexpr (PAR) {
+      const long long m = m0 + row;
+      const int i = (int)(m >> lgW) & (g.H - 1), j = (int)m & (g.W - 1);
+      return ((((m >> (lgW + lgH)) << (lgH + 1)) + 2 * i + pa) << (lgW + 1)) +
+             2 * j + pb;
+    } else {
+      return m0 + row;
+    }
+  };
   auto epi_load = [&](int r, int slot) {
     const long long off =
-        ((m0 + r * RPR + wrow) * N + n0) * 2 + wchunk * 16;  // bytes
+        (yrow(r * RPR + wrow) * N + n0) * 2 + wchunk * 16;  // bytes
     if constexpr (HAS_ADD || HAS_BNS)
       av[slot] = *(const short8*)((const char*)addend + off);
     if constexpr (HAS_MASK)
@@ -448,7 +514,7 @@ void conv_fwd_glds_kernel(
           c[j] = v;
         }
       }
-      *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
+      *(short8*)((char*)(y + yrow(row) * N + n0) + wchunk * 16) = c;
     }
   } else {
     // Masked store plus the BN-backward sums.  A real loop over pairs of
@@ -470,7 +536,7 @@ void conv_fwd_glds_kernel(
         sdb[j] += gv;
         sdg[j] += gv * (bfbits2f(t[j]) - mu[j]) * rs[j];
       }
-      *(short8*)((char*)(y + (m0 + row) * N + n0) + wchunk * 16) = c;
+      *(short8*)((char*)(y + yrow(row) * N + n0) + wchunk * 16) = c;
     };
 #pragma unroll 1
     for (int r = 0; r < NR; r += PF) {
@@ -548,6 +614,27 @@ bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
   if (k > H || H % k) return false;
   return cg::halo_bytes((int)W) + 2 * 64 * cg::BK * 2 <=
          2 * (cg::BM + 64) * cg::BK * 2;
+}
+
+// Shape test of the parity-split stride-2 dgrad route (cg::
+// conv_fwd_glds_kernel, PAR).  Arguments are the FORWARD conv's: input dims
+// H x W (= dx), Cin = dx channels, Kout = dy channels, batch N.  Pure host
+// arithmetic, exported like conv_halo64_eligible.  Beyond the 3x3 / stride 2 /
+// pad 1 / even H, W form and the glds kernel's own conditions, the dy dims
+// H/2 and W/2 must be powers of two: the kernel maps tile rows to pixels with
+// shifts (ImageNet-size pyramids, 56 -> 28, keep the stuffed route).
+bool conv_dgrad_s2_parity_eligible(int64_t H, int64_t W, int64_t Cin,
+                                   int64_t Kout, int64_t R, int64_t S,
+                                   int64_t stride, int64_t pad, int64_t N) {
+  if (R != 3 || S != 3 || stride != 2 || pad != 1) return false;
+  if (N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return false;
+  const int64_t HO = H / 2, WO = W / 2;
+  if ((HO & (HO - 1)) || (WO & (WO - 1))) return false;
+  if (Kout < 64 || (Kout & (Kout - 1))) return false;  // dy channels
+  if (Cin <= 0 || Cin % 64) return false;              // dx channels
+  const int64_t Mc = N * HO * WO;                      // rows per class
+  if (Mc % cg::BM) return false;
+  return 4 * (Mc / cg::BM) <= 2147483647LL / 8;
 }
 
 // Host entry: returns true when handled.  y must be pre-allocated
@@ -632,12 +719,26 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
    : BN == 256 ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
    : BN == 128 ? &cg::conv_fwd_glds_kernel<128, ST, EP>       \
                : &cg::conv_fwd_glds_kernel<64, ST, EP>)
-  auto kern = bns                     ? CG_KERN(false, cg::EPI_MASK_BNSTATS)
+  // parity-split stride-2 dgrad; PDT_DGRAD_S2_PARITY=0 keeps the stuffed
+  // gather (read per call).  Here x is dy, y is dx and w the rotated weight
+  // [dx channels][R][S][dy channels]; pad is R - 1 - (the forward's pad).
+  const char* ep = getenv("PDT_DGRAD_S2_PARITY");
+  const bool par = !(ep && ep[0] == '0') && lgSt == 1 && stride == 1 &&
+                   (bns || !stats_ws) && HO == 2 * H && WO == 2 * W &&
+                   conv_dgrad_s2_parity_eligible(HO, WO, Kout, C, R, S, 2,
+                                                 R - 1 - pad, N_);
+#define CG_DGRAD(EP)                                                      \
+  (!par        ? CG_KERN(false, EP)                                       \
+   : BN == 256 ? &cg::conv_fwd_glds_kernel<256, false, EP, 0, true>       \
+   : BN == 128 ? &cg::conv_fwd_glds_kernel<128, false, EP, 0, true>       \
+               : &cg::conv_fwd_glds_kernel<64, false, EP, 0, true>)
+  auto kern = bns                     ? CG_DGRAD(cg::EPI_MASK_BNSTATS)
               : stats_ws              ? CG_KERN(true, cg::EPI_NONE)
-              : epi == cg::EPI_NONE   ? CG_KERN(false, cg::EPI_NONE)
-              : epi == cg::EPI_ADD    ? CG_KERN(false, cg::EPI_ADD)
-              : epi == cg::EPI_MASK   ? CG_KERN(false, cg::EPI_MASK)
-                                      : CG_KERN(false, cg::EPI_ADD_MASK);
+              : epi == cg::EPI_NONE   ? CG_DGRAD(cg::EPI_NONE)
+              : epi == cg::EPI_ADD    ? CG_DGRAD(cg::EPI_ADD)
+              : epi == cg::EPI_MASK   ? CG_DGRAD(cg::EPI_MASK)
+                                      : CG_DGRAD(cg::EPI_ADD_MASK);
+#undef CG_DGRAD
 #undef CG_KERN
 #undef CG_HALO
   hipLaunchKernelGGL(kern, grid, dim3(cg::THREADS), 0, stream, ptr16<bf16>(x),

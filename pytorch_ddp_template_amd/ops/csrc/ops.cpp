@@ -61,6 +61,11 @@ std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
 // conv_glds.hip: does a conv shape take the halo-resident 64-wide tile
 bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
                           int64_t R, int64_t S, int64_t stride, int64_t pad);
+// conv_glds.hip: does a conv's dgrad take the parity-split stride-2 route
+// (arguments are the forward conv's: input H x W, Cin, Kout, batch N)
+bool conv_dgrad_s2_parity_eligible(int64_t H, int64_t W, int64_t Cin,
+                                   int64_t Kout, int64_t R, int64_t S,
+                                   int64_t stride, int64_t pad, int64_t N);
 // gemm_f32.hip
 torch::Tensor bmm_nt_f32(torch::Tensor A, torch::Tensor B,
                          c10::optional<torch::Tensor> bias, bool relu);
@@ -345,6 +350,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_halo64_eligible", &conv_halo64_eligible, py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("Kout"), py::arg("R"),
         py::arg("S"), py::arg("stride"), py::arg("pad"));
+  m.def("conv_dgrad_s2_parity_eligible", &conv_dgrad_s2_parity_eligible,
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Kout"),
+        py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"),
+        py::arg("N"));
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("relu_fwd", &relu_fwd);
   m.def("relu_bwd", &relu_bwd);
