@@ -1315,26 +1315,43 @@ namespace g16 {
 // chunk ch's row r+RSHIFT tile — a (3+RSHIFT)-slot ring restages RSHIFT
 // tiles per chunk instead of three (WO=32: 12 glds vs 28; WO=16: 20),
 // except at image boundaries (full restage behind an extra barrier).
-template <typename T16, int RSHIFT = 0>
+// PATCH (WO 4 and 8, no ring: RSHIFT would be 8 / 4 output rows, nothing
+// survives a chunk): the three row-tiles of one chunk are the same input
+// rows shifted by one, so ONE x tile per buffer holds the zero-padded input
+// patch of the chunk's 32 output positions and the tap's kernel row becomes
+// a row offset into it.  A chunk is G groups of Rg = min(HO, 32/WO) output
+// rows of one image (G * Rg * WO = 32; G = 2 only at HO = WO = 4, two
+// images); a group's patch is (Rg+2) rows x (WO+2) columns, stored as
+// q = g*(Rg+2)*(WO+2) + pr*(WO+2) + pc rows of [16 ch] gathering
+// x[n, ho0-pad+pr, pc-pad, :] — 60 q rows (G = 1) or 72 (G = 2) in a 96-row
+// image.  Tile rt of the three-tile layout is this tile from row rt*(WO+2)
+// on, so fragment reads, MFMA order and the block's partial sum are those of
+// the three-tile kernel bit for bit; per chunk 4 dy + 8 (G = 1) or 12 (G = 2)
+// x glds replace 28, and LDS is 2 x 16 KiB instead of 56 KiB.
+template <typename T16, int RSHIFT = 0, bool PATCH = false>
 __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
     const T16* __restrict__ dy, const T16* __restrict__ x,
     float* __restrict__ dw, const T16* __restrict__ zpad, int Mtot,
     int I /*Kout*/, int J /*Cin*/, long long ldc, ConvMeta cm, int lgWO,
     int lgHO, int zsplit) {
+  static_assert(!(PATCH && RSHIFT > 0), "the patch tile has no ring");
   constexpr bool RING = RSHIFT > 0;
   constexpr int SLOTS = 3 + RSHIFT;
   constexpr int BI = 64, BJ = 64, BMC = 32;
   constexpr int IMG_A = 32 * 16;   // dy images: [32 m][16 ch]
   constexpr int IMG_X = 64 * 16;   // x images: [<=48 q rows][16 ch], padded
+  constexpr int IMG_XP = 96 * 16;  // PATCH x images: [<=72 q rows][16 ch]
   constexpr int TILE_A = 4 * IMG_A;       // 4 KiB
   constexpr int TILE_X = 4 * IMG_X;       // 8 KiB per kernel row r
+  constexpr int TILE_XP = 4 * IMG_XP;     // 12 KiB, all three kernel rows
   typedef short v4s __attribute__((ext_vector_type(4)));
   using vec16 = typename M16<T16>::vec;
-  // RING layout: [2 dy bufs][4 x rt-slots] = 40 KB; else the classic
-  // [2][dy + 3 x tiles] = 56 KB
+  // RING layout: [2 dy bufs][4 x rt-slots] = 40 KB; PATCH: [2][dy + patch]
+  // = 32 KB; else the classic [2][dy + 3 x tiles] = 56 KB
   __shared__ __attribute__((aligned(16)))
-      T16 lds[RING ? (2 * TILE_A + SLOTS * TILE_X)
-                   : 2 * (TILE_A + 3 * TILE_X)];
+      T16 lds[RING    ? (2 * TILE_A + SLOTS * TILE_X)
+              : PATCH ? 2 * (TILE_A + TILE_XP)
+                      : 2 * (TILE_A + 3 * TILE_X)];
 
   // XCD-contiguous remap (private per-XCD L2s — see gemm_wgrad_tr_kernel):
   // blocks sharing a zidx read the same dy/x chunks; keep them on one L2.
@@ -1373,6 +1390,11 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
   const int segs = max(1, 32 >> lgL);
   const int E = segs * (L + 2);
   const int rcpL2 = 65536 / (L + 2) + 1;  // magic recip (q <= 63)
+  // PATCH geometry (lgWO 2 or 3, so L = WO): groups of 2^lgGs positions
+  const int lgGs = min(lgHO, 5 - lgWO) + lgWO;  // lg(Rg * WO), 4 or 5
+  const int PG = ((1 << (lgGs - lgWO)) + 2) * (L + 2);  // q rows per group
+  const int EP = (32 >> lgGs) * PG;                     // 60 or 72
+  const int nxp = (EP + 31) >> 5;                       // glds per x image
 
   f32x16 acc[9] = {};
 
@@ -1425,8 +1447,52 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
           16, 0, 0);
     }
   };
+  // PATCH: wave w stages dy image w (1 glds) and x image w (nxp glds)
+  auto stage_patch = [&](int buf, int ch) {
+    if (!PATCH) return;
+    const int m0 = ch * BMC;
+    T16* base = lds + buf * (TILE_A + TILE_XP);
+    {
+      const T16* src = zpad;
+      const int gm = m0 + sm;
+      const int ii = i0 + wave * 16 + sh8;
+      if (gm < Mtot && ii < I) src = dy + (long long)gm * I + ii;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)src,
+          (__attribute__((address_space(3))) unsigned int*)(
+              base + wave * IMG_A),
+          16, 0, 0);
+    }
+    for (int g3 = 0; g3 < nxp; ++g3) {
+      const int q = g3 * 32 + sm;  // lds row within the image
+      const T16* src = zpad;
+      if (q < EP) {
+        const int g = q >= PG ? 1 : 0;  // at most two groups
+        const int r = q - g * PG;
+        const int pr = (r * rcpL2) >> 16;
+        const int pc = r - pr * (L + 2);
+        const long long m_g = (long long)m0 + ((long long)g << lgGs);
+        if (m_g < Mtot) {
+          const long long t = m_g >> lgWO;  // group starts at column 0
+          const int ho0 = (int)(t & ((1 << lgHO) - 1));
+          const int n = (int)(t >> lgHO);
+          const int hi = ho0 - cm.pad + pr;
+          const int wi = pc - cm.pad;
+          const int jj = j0 + wave * 16 + sh8;
+          if (hi >= 0 && hi < cm.H && wi >= 0 && wi < cm.W && jj < Cin)
+            src = x + (((long long)n * cm.H + hi) * cm.W + wi) * Cin + jj;
+        }
+      }
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)src,
+          (__attribute__((address_space(3))) unsigned int*)(
+              base + TILE_A + wave * IMG_XP + g3 * (32 * 16)),
+          16, 0, 0);
+    }
+  };
   auto stage = [&](int buf, int ch) {
     if (RING) return;
+    if (PATCH) return stage_patch(buf, ch);
     const int m0 = ch * BMC;
     T16* base = lds + buf * (TILE_A + 3 * TILE_X);
     for (int u = wave; u < 4 + 24; u += 4) {
@@ -1479,7 +1545,12 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
   for (int kh = 0; kh < 2; ++kh) {
     const int mw = kh * 16 + ks * 8;
     qw[kh] = (mw >> lgL) * (L + 2) + (mw & (L - 1));
+    if (PATCH) {  // group, then row and column inside the group's patch
+      const int w = mw & ((1 << lgGs) - 1);
+      qw[kh] = (mw >> lgGs) * PG + (w >> lgL) * (L + 2) + (w & (L - 1));
+    }
   }
+  const int rt_rows = PATCH ? L + 2 : 0;  // PATCH: kernel row = row offset
 #define LDS_BYTE(p)                                           \
   ((unsigned)(unsigned long long)(__attribute__((            \
       address_space(3))) const T16*)(p))
@@ -1515,8 +1586,9 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
         stage(buf ^ 1, ch + 1);
       }
     }
-    const T16* base = RING ? lds + buf * TILE_A
-                           : lds + buf * (TILE_A + 3 * TILE_X);
+    const T16* base = RING    ? lds + buf * TILE_A
+                      : PATCH ? lds + buf * (TILE_A + TILE_XP)
+                              : lds + buf * (TILE_A + 3 * TILE_X);
 
     // A fragments (dy): 4 tr reads issued, drained by the FIRST counted
     // wait of the B pipeline below (not a full lgkmcnt(0) drain)
@@ -1556,12 +1628,14 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
         const int rt = idx / 6;
         const int rem = idx % 6, s2 = rem >> 1, kh = rem & 1;
         const T16* timg =
-            RING ? lds + 2 * TILE_A + ((r0 + rt) % SLOTS) * TILE_X +
-                       (img_sel + (wn >> 4)) * IMG_X
-                 : base + TILE_A + rt * TILE_X +
-                       (img_sel + (wn >> 4)) * IMG_X;
-        const unsigned b0 =
-            LDS_BYTE(timg) + (unsigned)((qw[kh] + s2) * 32) + lane_b;
+            RING    ? lds + 2 * TILE_A + ((r0 + rt) % SLOTS) * TILE_X +
+                          (img_sel + (wn >> 4)) * IMG_X
+            : PATCH ? base + TILE_A + (img_sel + (wn >> 4)) * IMG_XP
+                    : base + TILE_A + rt * TILE_X +
+                          (img_sel + (wn >> 4)) * IMG_X;
+        const unsigned b0 = LDS_BYTE(timg) +
+                            (unsigned)((qw[kh] + rt * rt_rows + s2) * 32) +
+                            lane_b;
         asm volatile(
             "ds_read_b64_tr_b16 %0, %2 offset:0\n\t"
             "ds_read_b64_tr_b16 %1, %3 offset:0"
@@ -1624,6 +1698,24 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_wgrad_seg_kernel(
 }
 }  // namespace g16
 
+// Shape test of the patch-staged 3x3 stride-1 wgrad route
+// (g16::gemm_wgrad_seg_kernel, PATCH).  Arguments are the forward conv's.
+// Pure host arithmetic, exported like conv_dgrad_s2_parity_eligible; the
+// launcher below takes the route exactly when this holds and
+// PDT_WGRAD_PATCH != "0".  Output map a power of two with WO 4 or 8 and
+// HO >= 4 (a chunk of 32 positions is then whole output rows of one image,
+// or two whole 4x4 images), Cin a power of two >= 8 as for every 16-bit
+// wgrad kernel; Kout is free (padded to a multiple of 8 by the caller).
+bool conv_wgrad_patch_eligible(int64_t H, int64_t W, int64_t Cin,
+                               int64_t Kout, int64_t R, int64_t S,
+                               int64_t stride, int64_t pad) {
+  if (R != 3 || S != 3 || stride != 1 || pad < 0 || Kout <= 0) return false;
+  const int64_t HO = H + 2 * pad - 2, WO = W + 2 * pad - 2;
+  if (H <= 0 || W <= 0 || HO < 4 || (HO & (HO - 1))) return false;
+  if (WO != 4 && WO != 8) return false;
+  return Cin >= 8 && !(Cin & (Cin - 1));
+}
+
 // conv wgrad: dw[Kout,R,S,C] (f32) from dy[N,HO,WO,Kout], x[N,H,W,C]
 torch::Tensor conv2d_wgrad_bf16(torch::Tensor dy, torch::Tensor x,
                                 int64_t stride, int64_t pad, int64_t R,
@@ -1677,9 +1769,18 @@ torch::Tensor conv2d_wgrad_bf16(torch::Tensor dy, torch::Tensor x,
       static const char* e_rg = getenv("PDT_WGRAD_RING");
       const bool ring =
           !(e_rg && e_rg[0] == '0') && lgWO >= 4 && lgHO >= 1;
+      // WO 4 / 8 (the ring has nothing to keep there): one x patch per
+      // chunk instead of three row-tiles, 12-16 glds instead of 28.
+      // PDT_WGRAD_PATCH=0 (read per call, for A/B runs in one process)
+      // keeps the three-tile kernel.
+      const char* e_pt = getenv("PDT_WGRAD_PATCH");
+      const bool patch =
+          !(e_pt && e_pt[0] == '0') &&
+          conv_wgrad_patch_eligible(H, W, Cin, Kout, R, S, stride, pad);
       auto kern = ring && lgWO == 5   ? &g16::gemm_wgrad_seg_kernel<t16, 1>
                   : ring && lgWO == 4 ? &g16::gemm_wgrad_seg_kernel<t16, 2>
-                                      : &g16::gemm_wgrad_seg_kernel<t16>;
+                  : patch ? &g16::gemm_wgrad_seg_kernel<t16, 0, true>
+                          : &g16::gemm_wgrad_seg_kernel<t16>;
       hipLaunchKernelGGL(kern, grid, dim3(g16::THREADS), 0, stream, dyp, xp,
                          dwp, zpp, M, Kout, Cin, ldc, cm, lgWO, lgHO,
                          (int)grid.z);

@@ -66,6 +66,10 @@ bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
 bool conv_dgrad_s2_parity_eligible(int64_t H, int64_t W, int64_t Cin,
                                    int64_t Kout, int64_t R, int64_t S,
                                    int64_t stride, int64_t pad, int64_t N);
+// gemm_bf16.hip: does a 16-bit conv's wgrad take the patch-staged seg kernel
+bool conv_wgrad_patch_eligible(int64_t H, int64_t W, int64_t Cin,
+                               int64_t Kout, int64_t R, int64_t S,
+                               int64_t stride, int64_t pad);
 // gemm_f32.hip
 torch::Tensor bmm_nt_f32(torch::Tensor A, torch::Tensor B,
                          c10::optional<torch::Tensor> bias, bool relu);
@@ -354,6 +358,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Kout"),
         py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"),
         py::arg("N"));
+  m.def("conv_wgrad_patch_eligible", &conv_wgrad_patch_eligible,
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Kout"),
+        py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"));
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("relu_fwd", &relu_fwd);
   m.def("relu_bwd", &relu_bwd);
