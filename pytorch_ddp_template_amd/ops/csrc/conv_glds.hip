@@ -27,7 +27,8 @@
 // Covers every non-stem ResNet-18/CIFAR conv (fwd and, via the rotated-
 // weight identity, stride-1 dgrad).  Reference scope: SURVEY §2b conv row.
 //
-// Halo-resident A (template parameter HW, 64-wide tile only): the per-tap
+// Halo-resident A (template parameter HW; the 64-wide tile, and the 128-wide
+// tile at HW = 16): the per-tap
 // gather above re-reads every input element once per tap, and the engine is
 // bound by that cache-to-LDS fill, not by MFMA or HBM (profiles/
 // r06_conv_halo64.md).  For 3x3 stride-1 pad-1 convs with C = 64 whose M-tile
@@ -36,7 +37,10 @@
 // streams only the 8-KB weight tile of each tap; same K order, same MFMA
 // sequence per output element, every epilogue shared, so results are
 // bit-identical to the per-tap route.  PDT_CONV_HALO64=0 (read per call)
-// restores the per-tap route for A/B runs.
+// restores the per-tap route for A/B runs.  The 128-wide tile does the same
+// for C = 128 on 16-wide images (conv_halo128_eligible, PDT_CONV_HALO128=0;
+// profiles/r09_conv_halo128.md): the 18 x 18 patch is two 64-channel planes
+// and the K-loop streams the 16-KB weight tile of each (tap, channel slice).
 //
 // Parity-split stride-2 dgrad (template parameter PAR, all three tile widths,
 // the five dgrad epilogue modes): a 3x3 stride-2 pad-1 dgrad run as a stride-1
@@ -105,6 +109,16 @@ constexpr int EPI_BNSTATS = 4, EPI_MASK_BNSTATS = EPI_MASK | EPI_BNSTATS;
 // 8 of an odd one: all 16 slots of the 256-B bank row, conflict-free for any
 // tap shift.  A tap (r, s) is then the per-lane address of column shift s
 // plus the constant (r * HP + ...) * 128 — no address arithmetic in the loop.
+//
+// 128-wide tile (BN = 128, HW = 16, C = 128): BN / 64 = 2 such planes, plane p
+// holding channels 64p .. 64p + 63 in exactly the layout above and starting
+// at p * halo_bytes(16) = p * 55,296 B.  That offset is a multiple of 1 KiB,
+// so a plane-1 read hits the banks of the same read in plane 0 and the
+// conflict-free enumeration above carries over unchanged.  K stays tap-major,
+// then the two 64-channel slices (kt = tap * 2 + slice), so a step adds its
+// slice's plane offset to the tap's address and streams weight tile kt.
+// 110,592 B of patch + 2 x 16 KB of weight buffers = 143,360 B: one block per
+// CU, as on the per-tap 128-wide tile.
 constexpr int halo_pitch(int hw) { return (hw + 2 + 7) & ~7; }
 constexpr int halo_bytes(int hw) {
   return hw ? (BM / hw + 2) * halo_pitch(hw) * BK * 2 : 0;
@@ -127,10 +141,12 @@ constexpr int halo_bytes(int hw) {
 // index, so every XCD gets the same mix of 1-, 2- and 4-tap tiles and the
 // four classes of one position tile read the same dy rows through one L2.
 //
-// (the second launch bound is waves per SIMD: the halo variant asks for the 4
-// that two co-resident blocks need, i.e. at most 128 VGPRs)
+// (the second launch bound is waves per SIMD: the 64-wide halo variant asks
+// for the 4 that two co-resident blocks need, i.e. at most 128 VGPRs; the
+// 128-wide one runs one block per CU)
 template <int BN, bool STATS, int EPI = EPI_NONE, int HW = 0, bool PAR = false>
-__global__ __launch_bounds__(THREADS, HW ? 4 : BN == 64 ? 2 : 1)
+__global__ __launch_bounds__(THREADS,
+                             HW ? (BN == 64 ? 4 : 1) : BN == 64 ? 2 : 1)
 void conv_fwd_glds_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, const __hip_bfloat16* __restrict__ zpad,
@@ -143,13 +159,16 @@ void conv_fwd_glds_kernel(
                 "dgrad epilogues carry no forward stats");
   static_assert(!(EPI & EPI_BNSTATS) || EPI == EPI_MASK_BNSTATS,
                 "BN-backward sums ride only with the mask, without an addend");
-  static_assert(HW == 0 || (BN == 64 && BM % HW == 0 && HW % 16 == 0),
-                "halo variant: 64-wide tile, whole image rows per M-tile");
+  static_assert(HW == 0 || ((BN == 64 || (BN == 128 && HW == 16)) &&
+                            BM % HW == 0 && HW % 16 == 0),
+                "halo variant: 64-wide tile, or 128-wide at HW = 16; whole "
+                "image rows per M-tile");
   static_assert(!PAR || (!STATS && HW == 0),
                 "parity split: dgrad only, per-tap gather");
-  constexpr int HALO_ELEMS = halo_bytes(HW) / 2;
+  constexpr int HALO_ELEMS = halo_bytes(HW) / 2;  // one 64-channel plane
+  constexpr int NPL = HW ? BN / 64 : 0;           // planes (host: C == BN)
   __shared__ __hip_bfloat16
-      smem[HW ? HALO_ELEMS + 2 * BN * BK : 2 * (BM + BN) * BK];
+      smem[HW ? NPL * HALO_ELEMS + 2 * BN * BK : 2 * (BM + BN) * BK];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -313,8 +332,10 @@ void conv_fwd_glds_kernel(
     constexpr int HP = halo_pitch(HW);
     constexpr int KR = BM / HW;                 // image rows per M-tile
     constexpr int PPR = HP / 8;                 // 1-KiB pieces per halo row
-    constexpr int NPIECE = (KR + 2) * PPR;
-    __hip_bfloat16* sw = smem + HALO_ELEMS;     // two weight tiles
+    constexpr int PLPIECE = (KR + 2) * PPR;     // pieces per plane
+    constexpr int NPIECE = NPL * PLPIECE;
+    constexpr int LGCH = BN == 64 ? 6 : 7;      // log2 C: the position stride
+    __hip_bfloat16* sw = smem + NPL * HALO_ELEMS;  // two weight tiles
     const int tpi = g.H / KR;                   // M-tiles per image
     const int tile = (int)(m0 / BM);            // host: M / BM fits an int
     const long long img = tile / tpi;
@@ -335,19 +356,23 @@ void conv_fwd_glds_kernel(
       }
     };
     stage_w(0, 0);
-    // piece pc = 8 positions of halo row pc / PPR; lane: position lane & 7,
-    // chunk lane >> 3.  Rows outside the image, the two border columns and
-    // the pitch padding come from the zero page.
+    // piece pc = 8 positions of halo row pc / PPR (of plane pc / PLPIECE, the
+    // planes being PLPIECE KiB apart); lane: position lane & 7, chunk
+    // lane >> 3.  Rows outside the image, the two border columns and the
+    // pitch padding come from the zero page.
 #pragma unroll
     for (int p0 = 0; p0 < NPIECE; p0 += 8) {
       const int pc = p0 + wave;
       if (pc < NPIECE) {
-        const int hr = pc / PPR;
+        const int pl = NPL > 1 ? pc / PLPIECE : 0;
+        const int pp = pc - pl * PLPIECE;
+        const int hr = pp / PPR;
         const int hi = h0 - 1 + hr;
-        const int wi = (pc - hr * PPR) * 8 + (lane & 7) - 1;
+        const int wi = (pp - hr * PPR) * 8 + (lane & 7) - 1;
         const __hip_bfloat16* src = zpad;
         if ((unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)HW)
-          src = x + (((img * g.H + hi) * HW + wi) << 6) + (lane >> 3) * 8;
+          src = x + (((img * g.H + hi) * HW + wi) << LGCH) + pl * 64 +
+                (lane >> 3) * 8;
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) unsigned int*)src,
             (__attribute__((address_space(3))) unsigned int*)(smem + pc * 512),
@@ -364,17 +389,21 @@ void conv_fwd_glds_kernel(
     }
     __syncthreads();
 
-    // tap-major K, one tap per 64-deep step: a real loop over the tap rows
-    // (fully unrolled, the dgrad epilogue modes spill), the three column
-    // shifts unrolled so that their offsets stay immediates
+    // tap-major K, one (tap, 64-channel slice) per 64-deep step: a real loop
+    // over the tap rows (fully unrolled, the dgrad epilogue modes spill), the
+    // three column shifts and the slices unrolled so that their offsets stay
+    // immediates
 #pragma unroll 1
     for (int rt = 0; rt < 3; ++rt)
 #pragma unroll
-    for (int st = 0; st < 3; ++st) {
-      const int kt = rt * 3 + st;
-      if (kt + 1 < 9) stage_w((kt + 1) & 1, kt + 1);
+    for (int st = 0; st < 3; ++st)
+#pragma unroll
+    for (int sl = 0; sl < NPL; ++sl) {
+      const int kt = (rt * 3 + st) * NPL + sl;
+      if (kt + 1 < 9 * NPL) stage_w((kt + 1) & 1, kt + 1);
       const __hip_bfloat16* sb = sw + (kt & 1) * (BN * BK);
-      const char* ha = (const char*)smem + rt * (HP * 128) + abase[st];
+      const char* ha = (const char*)smem + sl * (HALO_ELEMS * 2) +
+                       rt * (HP * 128) + abase[st];
       bf16x8 bf[NI][2];
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
@@ -616,6 +645,18 @@ bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
          2 * (cg::BM + 64) * cg::BK * 2;
 }
 
+// Shape test of the halo-resident A route of the 128-wide tile (cg::
+// conv_fwd_glds_kernel<128, *, *, 16>), same conventions as
+// conv_halo64_eligible.  A 256-row M-tile is one 16 x 16 slab of an image, its
+// patch two 64-channel planes: C = 128 and W = 16 only (143,360 B of LDS).
+bool conv_halo128_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
+                           int64_t R, int64_t S, int64_t stride, int64_t pad) {
+  if (R != 3 || S != 3 || stride != 1 || pad != 1 || C != 128) return false;
+  if (Kout <= 0 || Kout % 128 || Kout % 256 == 0) return false;  // BN == 128
+  if (W != 16) return false;
+  return H >= 16 && H % 16 == 0;
+}
+
 // Shape test of the parity-split stride-2 dgrad route (cg::
 // conv_fwd_glds_kernel, PAR).  Arguments are the FORWARD conv's: input dims
 // H x W (= dx), Cin = dx channels, Kout = dy channels, batch N.  Pure host
@@ -710,12 +751,18 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
   const char* eh = getenv("PDT_CONV_HALO64");
   const bool halo = !(eh && eh[0] == '0') && lgSt == 0 && H == HO && W == WO &&
                     conv_halo64_eligible(H, W, C, Kout, R, S, stride, pad);
+  // the same on the 128-wide tile (C = 128, W = 16); PDT_CONV_HALO128=0
+  const char* eh2 = getenv("PDT_CONV_HALO128");
+  const bool halo128 = !(eh2 && eh2[0] == '0') && lgSt == 0 && H == HO &&
+                       W == WO &&
+                       conv_halo128_eligible(H, W, C, Kout, R, S, stride, pad);
 #define CG_HALO(ST, EP)                                       \
   (W == 16   ? &cg::conv_fwd_glds_kernel<64, ST, EP, 16>      \
    : W == 32 ? &cg::conv_fwd_glds_kernel<64, ST, EP, 32>      \
              : &cg::conv_fwd_glds_kernel<64, ST, EP, 64>)
 #define CG_KERN(ST, EP)                                       \
   (halo        ? CG_HALO(ST, EP)                              \
+   : halo128   ? &cg::conv_fwd_glds_kernel<128, ST, EP, 16>   \
    : BN == 256 ? &cg::conv_fwd_glds_kernel<256, ST, EP>       \
    : BN == 128 ? &cg::conv_fwd_glds_kernel<128, ST, EP>       \
                : &cg::conv_fwd_glds_kernel<64, ST, EP>)

@@ -61,6 +61,9 @@ std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
 // conv_glds.hip: does a conv shape take the halo-resident 64-wide tile
 bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
                           int64_t R, int64_t S, int64_t stride, int64_t pad);
+// conv_glds.hip: the same for the halo-resident 128-wide tile (C = 128)
+bool conv_halo128_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
+                           int64_t R, int64_t S, int64_t stride, int64_t pad);
 // conv_glds.hip: does a conv's dgrad take the parity-split stride-2 route
 // (arguments are the forward conv's: input H x W, Cin, Kout, batch N)
 bool conv_dgrad_s2_parity_eligible(int64_t H, int64_t W, int64_t Cin,
@@ -352,6 +355,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
         py::arg("pad") = 0, py::arg("relu") = false);
   m.def("conv_halo64_eligible", &conv_halo64_eligible, py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("Kout"), py::arg("R"),
+        py::arg("S"), py::arg("stride"), py::arg("pad"));
+  m.def("conv_halo128_eligible", &conv_halo128_eligible, py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("Kout"), py::arg("R"),
         py::arg("S"), py::arg("stride"), py::arg("pad"));
   m.def("conv_dgrad_s2_parity_eligible", &conv_dgrad_s2_parity_eligible,
