@@ -41,7 +41,13 @@ from torch.utils.data import DataLoader
 
 from .data import CudaPrefetcher, ShardedSampler, build_dataset
 from .models import build_model
-from .optim import SGD, clip_grad_norm_, get_linear_schedule_with_warmup
+from .optim import (
+    SGD,
+    AdamW,
+    clip_grad_norm_,
+    get_linear_schedule_with_warmup,
+    param_groups_no_decay,
+)
 from .ops import scale_grads_
 from .ops import CrossEntropyLoss, MSELoss
 from .parallel import DistributedModel
@@ -515,13 +521,22 @@ def train(args, model):
 
     criterion = _criterion_for(args)
     use_master = args.bf16 or args.fp16
-    optimizer = SGD(
-        model.parameters(),
-        lr=args.learning_rate,
-        momentum=args.momentum,
-        weight_decay=args.weight_decay,
-        master_weights=use_master,
-    )
+    if args.optimizer == "adamw":
+        optimizer = AdamW(
+            param_groups_no_decay(model, args.weight_decay),
+            lr=args.learning_rate,
+            betas=(args.adam_beta1, args.adam_beta2),
+            eps=args.adam_epsilon,
+            master_weights=use_master,
+        )
+    else:
+        optimizer = SGD(
+            model.parameters(),
+            lr=args.learning_rate,
+            momentum=args.momentum,
+            weight_decay=args.weight_decay,
+            master_weights=use_master,
+        )
     scheduler = get_linear_schedule_with_warmup(
         optimizer, num_warmup_steps=args.warmup_steps, num_training_steps=t_total
     )
@@ -810,6 +825,13 @@ def build_parser():
     parser.add_argument("--learning_rate", "--lr", type=float, default=1e-3)
     parser.add_argument("--momentum", type=float, default=0.0)
     parser.add_argument("--weight_decay", type=float, default=0.0)
+    parser.add_argument("--optimizer", choices=("sgd", "adamw"), default="sgd",
+                        help="sgd (fused SGD/momentum) | adamw (fused AdamW; "
+                             "biases, norm params and the model's "
+                             "no_weight_decay() names are not decayed)")
+    parser.add_argument("--adam_beta1", type=float, default=0.9)
+    parser.add_argument("--adam_beta2", type=float, default=0.999)
+    parser.add_argument("--adam_epsilon", type=float, default=1e-8)
     parser.add_argument("--bf16", action="store_true",
                         help="bf16 weights/activations with fp32 master weights")
     parser.add_argument("--resume_from", type=str, default=None)
@@ -825,7 +847,7 @@ def build_parser():
     parser.add_argument("--eval_max_batches", type=int, default=None)
     parser.add_argument("--hip_graph", action="store_true",
                         help="capture the ws=1 training step in a hipGraph "
-                             "(fwd+bwd+clip+fused SGD replayed per step; "
+                             "(fwd+bwd+clip+fused optimizer replayed per step; "
                              "live LR via device scalar)")
     parser.add_argument("--prefetch", dest="prefetch", action="store_true",
                         default=True,

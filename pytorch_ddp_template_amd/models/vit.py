@@ -98,6 +98,11 @@ class ViT(nn.Module):
         self.norm = LayerNorm(dim)
         self.head = Linear(dim, num_classes)
 
+    def no_weight_decay(self):
+        """Parameter names that optim.param_groups_no_decay keeps out of
+        weight decay in addition to the ndim <= 1 ones."""
+        return {"cls_token", "pos_embed"}
+
     def _patchify(self, x):
         # NHWC (N, H, W, C) -> (N, n_patches, P*P*C)
         N, H, W, C = x.shape

@@ -4,6 +4,8 @@
 // ddp.py:183/240) as a fused multi-tensor kernel; global L2 grad norm +
 // scale for clip_grad_norm_ (ddp.py:238-239).  Supports bf16 params with
 // fp32 master weights (the apex-O2 slot, ddp.py:165-181, done natively).
+// AdamW (the reference's apex FusedAdam slot) runs on the same
+// machinery with its step count read from a device scalar.
 //
 // Chunking: tensor lists are flattened into fixed-size chunks dispatched to
 // blocks through a device-side descriptor table, so one launch covers the
@@ -11,6 +13,7 @@
 
 #include <torch/extension.h>
 
+#include <cmath>
 #include <vector>
 
 #include "common.h"
@@ -34,6 +37,7 @@ struct PtrTable {
   float* mom[kMaxTensors];
   float* master[kMaxTensors];
   long long numel[kMaxTensors];
+  float* aux[kMaxTensors];  // AdamW second moment (mom holds the first)
 };
 
 // ---- fused SGD (momentum / weight decay / dampening / nesterov) ----
@@ -112,6 +116,93 @@ __global__ void sgd_kernel(const ChunkDesc* __restrict__ chunks,
       gf = nesterov ? gf + momentum * mv : mv;
     }
     w -= lr * gf;
+    if (mw) mw[i] = w;
+    p[i] = to_t<T>(w);
+  }
+}
+
+// ---- fused AdamW (decoupled weight decay, torch.optim.AdamW rule) ----
+// Per-launch constants, the same for every element.
+struct AdamCoef {
+  float lr_wd;      // lr * wd
+  float b1, omb1;   // beta1, 1 - beta1 (1 - beta formed in double on the host)
+  float b2, omb2;
+  float step_size;  // lr / bc1
+  float sqrt_bc2;
+  float eps;
+};
+
+DEV_INLINE float adamw_update(float w, float g, float& m, float& v,
+                              const AdamCoef& c) {
+  w -= c.lr_wd * w;
+  m = c.b1 * m + c.omb1 * g;
+  v = c.b2 * v + c.omb2 * g * g;
+  w -= c.step_size * m / (sqrtf(v) / c.sqrt_bc2 + c.eps);
+  return w;
+}
+
+template <typename T>
+__global__ void adamw_kernel(const ChunkDesc* __restrict__ chunks,
+                             const PtrTable* __restrict__ tab, float lr,
+                             float b1, float omb1, float log_b1, float b2,
+                             float omb2, float log_b2, float eps, float wd,
+                             const float* __restrict__ step,
+                             const float* __restrict__ guard = nullptr,
+                             const float* __restrict__ lr_dev = nullptr) {
+  if (lr_dev != nullptr) lr = *lr_dev;
+  // A skipped step is a no-op here; the optimizer advances neither the step
+  // scalar nor the skip counter from this kernel (both tick once per step()
+  // on the host side of the launch, however many plans a step needs).
+  if (guard != nullptr && !isfinite(*guard)) return;
+  // bias corrections 1 - beta^t from the LIVE device step count, through
+  // expm1 of t * log(beta) (log taken in double on the host) so that small t
+  // does not cancel; beta == 0 gives log = -inf and bc = 1.
+  const float t = *step;
+  AdamCoef c;
+  c.lr_wd = lr * wd;
+  c.b1 = b1;
+  c.omb1 = omb1;
+  c.b2 = b2;
+  c.omb2 = omb2;
+  c.step_size = lr / -expm1f(t * log_b1);
+  c.sqrt_bc2 = sqrtf(-expm1f(t * log_b2));
+  c.eps = eps;
+  const ChunkDesc d = chunks[blockIdx.x];
+  const long long n = tab->numel[d.tensor];
+  const long long base = d.off;
+  const long long end = min(n, base + (long long)kChunk);
+  const T* g = reinterpret_cast<const T*>(tab->grad[d.tensor]);
+  T* p = reinterpret_cast<T*>(tab->param[d.tensor]);
+  float* m = tab->mom[d.tensor];
+  float* v = tab->aux[d.tensor];
+  float* mw = tab->master[d.tensor];
+  const long long vend = base + ((end - base) & ~3LL);
+  for (long long i = base + (long long)threadIdx.x * 4; i < vend;
+       i += (long long)blockDim.x * 4) {
+    Q4<T> g4 = *reinterpret_cast<const Q4<T>*>(g + i);
+    F4 w4;
+    if (mw) w4 = *reinterpret_cast<const F4*>(mw + i);
+    Q4<T> p4;
+    if (!mw) p4 = *reinterpret_cast<const Q4<T>*>(p + i);
+    F4 m4 = *reinterpret_cast<const F4*>(m + i);
+    F4 v4 = *reinterpret_cast<const F4*>(v + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float w = mw ? w4.v[j] : to_f(p4.v[j]);
+      w = adamw_update(w, to_f(g4.v[j]), m4.v[j], v4.v[j], c);
+      w4.v[j] = w;
+      p4.v[j] = to_t<T>(w);
+    }
+    *reinterpret_cast<F4*>(m + i) = m4;
+    *reinterpret_cast<F4*>(v + i) = v4;
+    if (mw) *reinterpret_cast<F4*>(mw + i) = w4;
+    *reinterpret_cast<Q4<T>*>(p + i) = p4;
+  }
+  for (long long i = vend + threadIdx.x; i < end; i += blockDim.x) {
+    float mi = m[i], vi = v[i];
+    float w = adamw_update(mw ? mw[i] : to_f(p[i]), to_f(g[i]), mi, vi, c);
+    m[i] = mi;
+    v[i] = vi;
     if (mw) mw[i] = w;
     p[i] = to_t<T>(w);
   }
@@ -321,6 +412,103 @@ void sgd_step(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grad
           reinterpret_cast<const mt::PtrTable*>(plan.table_dev.data_ptr()),
           (float)lr, (float)momentum, (float)wd, (float)damp, nesterov ? 1 : 0,
           use_mom ? 1 : 0, guard_p, skip_p, lr_p);
+    });
+  }
+}
+
+// AdamW over a tensor list.  `step` is the optimizer's device step count
+// (already advanced for this step by the caller); see optim.AdamW.
+void adamw_step(std::vector<torch::Tensor> params,
+                std::vector<torch::Tensor> grads,
+                std::vector<torch::Tensor> exp_avgs,
+                std::vector<torch::Tensor> exp_avg_sqs,
+                std::vector<torch::Tensor> masters, double lr, double beta1,
+                double beta2, double eps, double wd, torch::Tensor step,
+                c10::optional<torch::Tensor> guard,
+                c10::optional<torch::Tensor> skip_count,
+                c10::optional<torch::Tensor> lr_tensor) {
+  TORCH_CHECK(!params.empty(), "adamw_step: empty parameter list");
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n &&
+                  exp_avg_sqs.size() == n && masters.size() == n,
+              "adamw_step: list lengths differ");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "adamw_step: betas must be in [0, 1)");
+  auto dev = params[0].device();
+  const auto dtype = params[0].scalar_type();
+  auto f32_scalar = [&](const torch::Tensor& t, const char* what) {
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == 1 &&
+                    t.device() == dev,
+                "adamw_step: ", what,
+                " must be a one-element f32 tensor on the params' device");
+    return t.data_ptr<float>();
+  };
+  auto f32_state = [&](const torch::Tensor& t, size_t i, const char* what) {
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                    t.numel() == params[i].numel() && t.device() == dev,
+                "adamw_step: ", what, "[", i,
+                "] must be contiguous f32 with the param's numel");
+    return t.data_ptr<float>();
+  };
+  const float* step_p = f32_scalar(step, "step");
+  const float* guard_p =
+      guard.has_value() ? f32_scalar(*guard, "guard") : nullptr;
+  // the skip counter is ticked by the caller once per step, never here
+  if (skip_count.has_value()) f32_scalar(*skip_count, "skip_count");
+  const float* lr_p =
+      lr_tensor.has_value() ? f32_scalar(*lr_tensor, "lr_tensor") : nullptr;
+  std::vector<float*> m_p(n), v_p(n), mw_p(n);
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(params[i].scalar_type() == dtype &&
+                    grads[i].scalar_type() == dtype,
+                "adamw_step: param/grad ", i, " dtype differs from params[0]");
+    TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous(),
+                "adamw_step: param/grad ", i, " is not contiguous");
+    TORCH_CHECK(grads[i].numel() == params[i].numel() &&
+                    params[i].device() == dev && grads[i].device() == dev,
+                "adamw_step: param/grad ", i, " numel or device mismatch");
+    m_p[i] = f32_state(exp_avgs[i], i, "exp_avgs");
+    v_p[i] = f32_state(exp_avg_sqs[i], i, "exp_avg_sqs");
+    mw_p[i] = (masters[i].defined() && masters[i].numel())
+                  ? f32_state(masters[i], i, "masters")
+                  : nullptr;
+  }
+  PlanKey key;
+  key.ptrs.reserve(6 * n + 2);
+  key.ptrs.push_back((const void*)0xADA3);  // op tag
+  key.ptrs.push_back((const void*)(uintptr_t)n);
+  for (size_t i = 0; i < n; ++i) {
+    key.ptrs.push_back(params[i].data_ptr());
+    key.ptrs.push_back(grads[i].data_ptr());
+    key.ptrs.push_back((const void*)(uintptr_t)params[i].numel());
+    key.ptrs.push_back(m_p[i]);
+    key.ptrs.push_back(v_p[i]);
+    key.ptrs.push_back(mw_p[i]);
+  }
+  const auto& plans = cached_plans(std::move(key), [&] {
+    return make_plans(params, dev,
+                      [&](size_t i, int local, mt::PtrTable* tab) {
+                        tab->grad[local] = grads[i].data_ptr();
+                        tab->param[local] = params[i].data_ptr();
+                        tab->mom[local] = m_p[i];
+                        tab->aux[local] = v_p[i];
+                        tab->master[local] = mw_p[i];
+                      });
+  });
+  // log(beta) in double: the kernel forms 1 - beta^t as -expm1(t * log beta)
+  const float log_b1 = (float)std::log(beta1);
+  const float log_b2 = (float)std::log(beta2);
+  auto stream = c10::hip::getCurrentHIPStream();
+  for (auto& plan : plans) {
+    DDP_DISPATCH_FLOAT(dtype, "adamw_step", [&] {
+      hipLaunchKernelGGL(
+          (mt::adamw_kernel<scalar_t>), dim3(plan.n_blocks), dim3(256), 0,
+          stream,
+          reinterpret_cast<const mt::ChunkDesc*>(plan.chunks_dev.data_ptr()),
+          reinterpret_cast<const mt::PtrTable*>(plan.table_dev.data_ptr()),
+          (float)lr, (float)beta1, (float)(1.0 - beta1), log_b1, (float)beta2,
+          (float)(1.0 - beta2), log_b2, (float)eps, (float)wd, step_p, guard_p,
+          lr_p);
     });
   }
 }

@@ -138,6 +138,15 @@ void sgd_step(std::vector<torch::Tensor> params,
               c10::optional<torch::Tensor> guard,
               c10::optional<torch::Tensor> skip_count,
               c10::optional<torch::Tensor> lr_tensor);
+void adamw_step(std::vector<torch::Tensor> params,
+                std::vector<torch::Tensor> grads,
+                std::vector<torch::Tensor> exp_avgs,
+                std::vector<torch::Tensor> exp_avg_sqs,
+                std::vector<torch::Tensor> masters, double lr, double beta1,
+                double beta2, double eps, double wd, torch::Tensor step,
+                c10::optional<torch::Tensor> guard,
+                c10::optional<torch::Tensor> skip_count,
+                c10::optional<torch::Tensor> lr_tensor);
 torch::Tensor l2norm_sq(std::vector<torch::Tensor> grads);
 void scale_(std::vector<torch::Tensor> ts, double s);
 void scale_by_tensor_(std::vector<torch::Tensor> ts, torch::Tensor s);
@@ -407,6 +416,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("moms"), py::arg("masters"), py::arg("lr"),
         py::arg("momentum"), py::arg("wd"), py::arg("damp"),
         py::arg("nesterov"), py::arg("guard") = py::none(),
+        py::arg("skip_count") = py::none(),
+        py::arg("lr_tensor") = py::none());
+  m.def("adamw_step", &adamw_step, py::arg("params"), py::arg("grads"),
+        py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("masters"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("step"), py::arg("guard") = py::none(),
         py::arg("skip_count") = py::none(),
         py::arg("lr_tensor") = py::none());
   m.def("l2norm_sq", &l2norm_sq);
