@@ -41,6 +41,7 @@ from torch.utils.data import DataLoader
 
 from .data import CudaPrefetcher, ShardedSampler, build_dataset
 from .models import build_model
+from .models import is_vit as _is_vit
 from .optim import (
     SGD,
     AdamW,
@@ -50,6 +51,7 @@ from .optim import (
 )
 from .ops import scale_grads_
 from .ops import CrossEntropyLoss, MSELoss
+from .ops import rng as philox_rng
 from .parallel import DistributedModel
 from .utils import (
     getLoggerWithRank,
@@ -71,13 +73,16 @@ logger = None
 def set_seed(args):
     """Seed random/numpy/torch (+ all GPUs) — reference ddp.py:44-49.
 
-    Same seed on every rank; shard divergence comes from the sampler.
+    Same seed on every rank; shard divergence comes from the sampler.  The
+    dropout generator (ops/rng.py) is keyed by (seed, global rank), so ranks
+    draw different masks.
     """
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     if args.n_gpu > 0:
         torch.cuda.manual_seed_all(args.seed)
+    philox_rng.manual_seed(args.seed, getattr(args, "node_rank", 0))
 
 
 def setup(args):
@@ -169,6 +174,7 @@ def save_checkpoint(
             "torch": torch.get_rng_state(),
             "numpy": np.random.get_state(),
             "random": random.getstate(),
+            "philox": philox_rng.get_state(),
         },
     }
     if scaler is not None:
@@ -243,6 +249,8 @@ def load_training_state(args, path, scaler=None):
         np.random.set_state(rng["numpy"])
     if "random" in rng:
         random.setstate(rng["random"])
+    if "philox" in rng:
+        philox_rng.set_state(rng["philox"])
     if "cuda" in rng and torch.cuda.is_available() and args.n_gpu > 0:
         try:
             torch.cuda.set_rng_state_all(rng["cuda"])
@@ -337,6 +345,10 @@ class GraphStep:
         self._warm = 0
 
     def _inner(self):
+        # one tick per step: every replay draws fresh dropout masks from the
+        # call ids baked into the graph (3 warm-ups + 1 capture pass that only
+        # records + N replays leave the scalar at 3 + N)
+        philox_rng.tick(self.x_st.device)
         out = self.model(self.x_st)
         loss = self.criterion(out, self.y_st)
         loss.backward()
@@ -832,6 +844,12 @@ def build_parser():
     parser.add_argument("--adam_beta1", type=float, default=0.9)
     parser.add_argument("--adam_beta2", type=float, default=0.999)
     parser.add_argument("--adam_epsilon", type=float, default=1e-8)
+    parser.add_argument("--dropout", type=float, default=0.0,
+                        help="ViT dropout rate (after the position embedding, "
+                             "on the attention projection and both MLP layers)")
+    parser.add_argument("--drop_path", type=float, default=0.0,
+                        help="ViT stochastic depth: rate of the last block, "
+                             "growing linearly from 0 at the first")
     parser.add_argument("--bf16", action="store_true",
                         help="bf16 weights/activations with fp32 master weights")
     parser.add_argument("--resume_from", type=str, default=None)
@@ -858,11 +876,19 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    for flag in ("dropout", "drop_path"):
+        rate = getattr(args, flag)
+        if not 0.0 <= rate < 1.0:
+            parser.error(f"--{flag} must be in [0, 1), got {rate}")
+        if rate and not _is_vit(args.model):
+            parser.error(f"--{flag} is only wired into vit-b16, "
+                         f"not --model {args.model}")
     if args.dataset is None:
         args.dataset = args.model
     setup(args)
-    model = build_model(args.model)
+    model = build_model(args.model, None, args.dropout, args.drop_path)
     train(args, model)
     cleanup(args)
     logger.info("Process exited.")

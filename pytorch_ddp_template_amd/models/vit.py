@@ -1,13 +1,26 @@
 """ViT-B/16 on the framework's HIP-backed ops (BASELINE.json config 5).
 
-Attention is composed from the framework's batched MFMA GEMM primitives
-(``bmm_nt`` / ``bmm_nn``) plus a fused row-softmax kernel — every
-matmul-shaped op runs on hand-written CDNA4 kernels, with the score matrix
-materialized (S=197 is small; a fused flash-style kernel is a later
-optimization, see SURVEY.md §7 rung 5).
+Attention runs in the fused flash-style kernel (``attention_qkv``: q/k/v
+staged straight from the packed qkv GEMM output, K/V tiled, no score matrix
+in memory) whenever the head size is 64 and the dtype is bf16/fp16 on the
+GPU; every other case (fp32, other head sizes, the CPU path) is composed
+from the batched GEMM primitives (``bmm_nt`` / ``bmm_nn``) plus the fused
+row-softmax kernel, with the score matrix materialized.
 
 Patch embedding is a Linear over unfolded 16x16x3 patches (= 768-dim
 vectors), which on NHWC input is a pure reshape + one GEMM — no conv needed.
+
+Regularisation (``dropout`` / ``drop_path``, both 0 by default): dropout
+after the position-embedding add, on the attention projection output, after
+the MLP's GELU and on the MLP output; stochastic depth on both residual
+branches of block ``i`` at rate ``drop_path * i / (depth - 1)``.  Each
+residual is ONE ``dropout_add`` kernel (element mask, per-sample mask and the
+add), masks come from the counter-based generator in ``ops/rng.py`` and are
+never stored.  With both rates 0, and in eval mode, the forward runs exactly
+the ops of the unregularised model; the modules hold no extra state, so
+``state_dict`` keys do not depend on the rates.  Not covered: dropout on the
+attention probabilities (it belongs inside the attention kernel), fusing the
+post-GELU dropout into the GELU kernel, label smoothing.
 """
 
 from __future__ import annotations
@@ -18,7 +31,7 @@ import torch
 from torch import nn
 
 from ..ops import GELU, LayerNorm, Linear
-from ..ops.functional import attention, attention_qkv
+from ..ops.functional import attention, attention_qkv, dropout, dropout_add
 from ..ops.native import native_available
 
 
@@ -54,8 +67,9 @@ class MultiHeadAttention(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, mlp_ratio=4):
+    def __init__(self, dim, heads, mlp_ratio=4, dropout=0.0, drop_path=0.0):
         super().__init__()
+        self.p, self.p_path = float(dropout), float(drop_path)
         self.norm1 = LayerNorm(dim)
         self.attn = MultiHeadAttention(dim, heads)
         self.norm2 = LayerNorm(dim)
@@ -66,9 +80,16 @@ class Block(nn.Module):
         )
 
     def forward(self, x):
-        x = x + self.attn(self.norm1(x))
-        x = x + self.mlp(self.norm2(x))
-        return x
+        if not self.training or (self.p == 0 and self.p_path == 0):
+            x = x + self.attn(self.norm1(x))
+            x = x + self.mlp(self.norm2(x))
+            return x
+        # mlp's members are called one by one (the Sequential keeps its
+        # state_dict keys); each residual is one dropout_add
+        x = dropout_add(self.attn(self.norm1(x)), x, self.p, self.p_path, True)
+        h = self.mlp[1](self.mlp[0](self.norm2(x)))
+        h = self.mlp[2](dropout(h, self.p, True))
+        return dropout_add(h, x, self.p, self.p_path, True)
 
 
 class ViT(nn.Module):
@@ -82,9 +103,12 @@ class ViT(nn.Module):
         mlp_ratio=4,
         num_classes=1000,
         in_ch=3,
+        dropout=0.0,
+        drop_path=0.0,
     ):
         super().__init__()
         assert image_size % patch_size == 0
+        self.p = float(dropout)
         self.patch_size = patch_size
         self.grid = image_size // patch_size
         n_patches = self.grid * self.grid
@@ -94,7 +118,12 @@ class ViT(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, n_patches + 1, dim) )
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.trunc_normal_(self.cls_token, std=0.02)
-        self.blocks = nn.Sequential(*[Block(dim, heads, mlp_ratio) for _ in range(depth)])
+        # stochastic depth grows linearly from 0 (first block) to drop_path
+        self.blocks = nn.Sequential(*[
+            Block(dim, heads, mlp_ratio, dropout,
+                  drop_path * i / max(depth - 1, 1))
+            for i in range(depth)
+        ])
         self.norm = LayerNorm(dim)
         self.head = Linear(dim, num_classes)
 
@@ -116,10 +145,12 @@ class ViT(nn.Module):
         x = self.patch_embed(self._patchify(x))
         cls = self.cls_token.to(x.dtype).expand(x.shape[0], -1, -1)
         x = torch.cat([cls, x], dim=1) + self.pos_embed.to(x.dtype)
+        x = dropout(x, self.p, self.training)
         x = self.blocks(x)
         x = self.norm(x)
         return self.head(x[:, 0])
 
 
-def vit_b16(num_classes=1000, image_size=224):
-    return ViT(image_size=image_size, num_classes=num_classes)
+def vit_b16(num_classes=1000, image_size=224, dropout=0.0, drop_path=0.0):
+    return ViT(image_size=image_size, num_classes=num_classes,
+               dropout=dropout, drop_path=drop_path)

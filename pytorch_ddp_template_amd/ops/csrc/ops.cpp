@@ -150,6 +150,14 @@ void adamw_step(std::vector<torch::Tensor> params,
 torch::Tensor l2norm_sq(std::vector<torch::Tensor> grads);
 void scale_(std::vector<torch::Tensor> ts, double s);
 void scale_by_tensor_(std::vector<torch::Tensor> ts, torch::Tensor s);
+// dropout.hip: out = (res or 0) + x * elem mask * row mask, Philox in-kernel
+torch::Tensor dropout_fwd(torch::Tensor x, c10::optional<torch::Tensor> res,
+                          c10::optional<torch::Tensor> out, torch::Tensor step,
+                          int64_t key0, int64_t key1, int64_t call_id_elem,
+                          int64_t call_id_row, double p_elem, double p_row,
+                          int64_t inner);
+int64_t dropout_grid_cap();
+int64_t dropout_block();
 
 // ======================= routing helpers =================================
 
@@ -427,6 +435,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_sq", &l2norm_sq);
   m.def("scale_", &scale_);
   m.def("scale_by_tensor_", &scale_by_tensor_);
+  m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("res"),
+        py::arg("out"), py::arg("step"), py::arg("key0"), py::arg("key1"),
+        py::arg("call_id_elem"), py::arg("call_id_row"), py::arg("p_elem"),
+        py::arg("p_row"), py::arg("inner"));
+  m.def("dropout_grid_cap", &dropout_grid_cap);
+  m.def("dropout_block", &dropout_block);
   m.def("im2col", &im2col);
   m.def("weight_rot", &weight_rot);
   m.def("zero_stuff", &zero_stuff);

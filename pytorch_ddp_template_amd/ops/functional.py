@@ -35,6 +35,7 @@ import os
 import torch
 import torch.nn.functional as F
 
+from . import rng
 from .native import native, use_native
 
 # ---------------------------------------------------------------------------
@@ -797,6 +798,101 @@ def attention(q, k, v, scale):
     """
     p = softmax(bmm_nt(q, k), scale)
     return bmm_nn(p, v)
+
+
+# ---------------------------------------------------------------------------
+# Dropout / stochastic depth (+ fused residual add), Philox in-kernel
+# ---------------------------------------------------------------------------
+
+
+def _dropout_apply(x, res, cid_e, cid_r, p, p_row, inner):
+    """(res or 0) + x * elem mask * row mask under the current rng state.
+    p == 0 / p_row == 0 switches that mask off; x (and res) contiguous."""
+    if use_native(x, res):
+        k0, k1 = rng.key()
+        return native().dropout_fwd(
+            x, res, None, rng.step_scalar(x.device), k0, k1, cid_e, cid_r,
+            float(p), float(p_row), inner,
+        )
+    # CPU path: the same bits from the same state (ops/rng.py)
+    step = int(rng.step_scalar(x.device).item())
+    n = x.numel()
+    t = x.float().reshape(-1)
+    zero = torch.zeros((), dtype=torch.float32, device=t.device)
+    if p > 0:
+        keep = rng.keep_mask(n, p, cid_e, step).to(t.device)
+        t = torch.where(keep, t * rng.keep_scale(p), zero)
+    if p_row > 0:
+        rows = n // inner if n else 0
+        keep = rng.keep_mask(rows, p_row, cid_r, step)
+        keep = keep.repeat_interleave(inner).to(t.device)
+        t = torch.where(keep, t * rng.keep_scale(p_row), zero)
+    if res is not None:
+        t = res.float().reshape(-1) + t
+    return t.to(x.dtype).reshape(x.shape)
+
+
+class _DropoutAddFn(torch.autograd.Function):
+    """out = (res or 0) + x * keep_elem * s_elem * keep_row * s_row.
+
+    No mask is stored: backward is the same kernel on dy with the same call
+    ids, rates and step scalar (nothing ticks between forward and backward),
+    and the residual's gradient is dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, res, p, p_row):
+        x = x.contiguous()
+        if res is not None:
+            res = res.contiguous()
+        # one call id per mask, so the two draws never share a word
+        ctx.cid_e = rng.next_call_id() if p > 0 else 0
+        ctx.cid_r = rng.next_call_id() if p_row > 0 else 0
+        ctx.p, ctx.p_row = p, p_row
+        ctx.inner = x.numel() // x.shape[0] if x.numel() else 1
+        ctx.has_res = res is not None
+        return _dropout_apply(x, res, ctx.cid_e, ctx.cid_r, p, p_row, ctx.inner)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _dropout_apply(dy.contiguous(), None, ctx.cid_e, ctx.cid_r,
+                                ctx.p, ctx.p_row, ctx.inner)
+        dres = dy if ctx.has_res and ctx.needs_input_grad[1] else None
+        return dx, dres, None, None
+
+
+def _check_rate(p, what):
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{what} rate must be in [0, 1), got {p}")
+
+
+def dropout(x, p, training=True):
+    """Elementwise dropout.  Eval mode or p == 0 returns x, launches nothing
+    and takes no call id."""
+    _check_rate(p, "dropout")
+    if not training or p == 0:
+        return x
+    return _DropoutAddFn.apply(x, None, float(p), 0.0)
+
+
+def drop_path(x, p, training=True):
+    """Stochastic depth: one draw per index of dim 0."""
+    _check_rate(p, "drop_path")
+    if not training or p == 0:
+        return x
+    return _DropoutAddFn.apply(x, None, 0.0, float(p))
+
+
+def dropout_add(x, res, p, p_path, training=True):
+    """res + drop_path(dropout(x, p), p_path) in one pass over the data."""
+    _check_rate(p, "dropout")
+    _check_rate(p_path, "drop_path")
+    if not training or (p == 0 and p_path == 0):
+        return res + x
+    if x.shape != res.shape or x.dtype != res.dtype:
+        raise ValueError("dropout_add: x and res must match in shape and dtype")
+    return _DropoutAddFn.apply(x, res, float(p), float(p_path))
 
 
 # ---------------------------------------------------------------------------

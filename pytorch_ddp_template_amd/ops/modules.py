@@ -51,6 +51,34 @@ class GELU(nn.Module):
         return X.gelu(x)
 
 
+class Dropout(nn.Module):
+    """Elementwise dropout with the mask drawn in the kernel (ops/rng.py)."""
+
+    def __init__(self, p=0.5):
+        super().__init__()
+        self.p = float(p)
+
+    def forward(self, x):
+        return X.dropout(x, self.p, self.training)
+
+    def extra_repr(self):
+        return f"p={self.p}"
+
+
+class DropPath(nn.Module):
+    """Stochastic depth: drops whole samples (indices of dim 0)."""
+
+    def __init__(self, p=0.0):
+        super().__init__()
+        self.p = float(p)
+
+    def forward(self, x):
+        return X.drop_path(x, self.p, self.training)
+
+    def extra_repr(self):
+        return f"p={self.p}"
+
+
 class Conv2dNHWC(nn.Module):
     """Conv2d on (N, H, W, C) tensors; weight stored (K, R, S, C)."""
 
