@@ -850,6 +850,10 @@ def build_parser():
     parser.add_argument("--drop_path", type=float, default=0.0,
                         help="ViT stochastic depth: rate of the last block, "
                              "growing linearly from 0 at the first")
+    parser.add_argument("--attn_dropout", type=float, default=0.0,
+                        help="ViT dropout rate on the attention probabilities "
+                             "(inside the fused attention kernels); 0 or at "
+                             "least 1/256")
     parser.add_argument("--bf16", action="store_true",
                         help="bf16 weights/activations with fp32 master weights")
     parser.add_argument("--resume_from", type=str, default=None)
@@ -878,17 +882,21 @@ def build_parser():
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    for flag in ("dropout", "drop_path"):
+    for flag in ("dropout", "drop_path", "attn_dropout"):
         rate = getattr(args, flag)
         if not 0.0 <= rate < 1.0:
             parser.error(f"--{flag} must be in [0, 1), got {rate}")
         if rate and not _is_vit(args.model):
             parser.error(f"--{flag} is only wired into vit-b16, "
                          f"not --model {args.model}")
+    if 0.0 < args.attn_dropout < 1.0 / 256.0:
+        parser.error("--attn_dropout below 1/256 would drop nothing "
+                     f"(one byte per element), got {args.attn_dropout}")
     if args.dataset is None:
         args.dataset = args.model
     setup(args)
-    model = build_model(args.model, None, args.dropout, args.drop_path)
+    model = build_model(args.model, None, args.dropout, args.drop_path,
+                        args.attn_dropout)
     train(args, model)
     cleanup(args)
     logger.info("Process exited.")

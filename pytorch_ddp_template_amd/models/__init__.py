@@ -8,15 +8,17 @@ def is_vit(name: str) -> bool:
 
 
 def build_model(name: str, num_classes: int | None = None,
-                dropout: float = 0.0, drop_path: float = 0.0):
+                dropout: float = 0.0, drop_path: float = 0.0,
+                attn_dropout: float = 0.0):
     """Factory used by the CLI / bench: name -> model instance.
 
-    ``dropout`` / ``drop_path`` are the ViT's regularisers; a nonzero rate
-    with any other model is an error."""
+    ``dropout`` / ``drop_path`` / ``attn_dropout`` are the ViT's regularisers;
+    a nonzero rate with any other model is an error."""
     name = name.lower()
-    if (dropout or drop_path) and not is_vit(name):
+    if (dropout or drop_path or attn_dropout) and not is_vit(name):
         raise ValueError(
-            f"dropout / drop_path are only wired into the ViT, not {name!r}"
+            "dropout / drop_path / attn_dropout are only wired into the ViT, "
+            f"not {name!r}"
         )
     if name in ("foo", "foomodel", "mlp"):
         return FooModel()
@@ -28,7 +30,7 @@ def build_model(name: str, num_classes: int | None = None,
         return resnet50(num_classes or 1000, stem="imagenet")
     if is_vit(name):
         return vit_b16(num_classes or 1000, dropout=dropout,
-                       drop_path=drop_path)
+                       drop_path=drop_path, attn_dropout=attn_dropout)
     raise ValueError(f"unknown model {name!r}")
 
 

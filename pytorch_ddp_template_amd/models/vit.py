@@ -18,9 +18,15 @@ residual is ONE ``dropout_add`` kernel (element mask, per-sample mask and the
 add), masks come from the counter-based generator in ``ops/rng.py`` and are
 never stored.  With both rates 0, and in eval mode, the forward runs exactly
 the ops of the unregularised model; the modules hold no extra state, so
-``state_dict`` keys do not depend on the rates.  Not covered: dropout on the
-attention probabilities (it belongs inside the attention kernel), fusing the
-post-GELU dropout into the GELU kernel, label smoothing.
+``state_dict`` keys do not depend on the rates.
+
+``attn_dropout`` (0 by default) is dropout on the attention probabilities.  On
+the fused route it happens inside the flash forward and backward kernels (the
+probabilities never exist in memory; both kernels regenerate the mask); the
+composed route applies the same mask to the materialized probabilities.
+
+Not covered: fusing the post-GELU dropout into the GELU kernel, label
+smoothing.
 """
 
 from __future__ import annotations
@@ -36,10 +42,11 @@ from ..ops.native import native_available
 
 
 class MultiHeadAttention(nn.Module):
-    def __init__(self, dim, heads):
+    def __init__(self, dim, heads, attn_dropout=0.0):
         super().__init__()
         assert dim % heads == 0
         self.dim, self.heads = dim, heads
+        self.p_attn = float(attn_dropout)
         self.qkv = Linear(dim, 3 * dim)
         self.proj = Linear(dim, dim)
 
@@ -57,21 +64,24 @@ class MultiHeadAttention(nn.Module):
             and native_available()
         ):
             # fused kernel: stages q/k/v straight from the packed qkv
-            out = attention_qkv(qkv.contiguous(), h, 1.0 / math.sqrt(dh))
+            out = attention_qkv(qkv.contiguous(), h, 1.0 / math.sqrt(dh),
+                                self.p_attn, self.training)
             return self.proj(out)
         qkv = qkv.reshape(N, S, 3, h, dh).permute(2, 0, 3, 1, 4)
         q, k, v = (t.reshape(N * h, S, dh).contiguous() for t in qkv)
-        out = attention(q, k, v, 1.0 / math.sqrt(dh))  # (N*h, S, dh)
+        out = attention(q, k, v, 1.0 / math.sqrt(dh), self.p_attn,
+                        self.training)  # (N*h, S, dh)
         out = out.reshape(N, h, S, dh).permute(0, 2, 1, 3).reshape(N, S, D)
         return self.proj(out)
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, mlp_ratio=4, dropout=0.0, drop_path=0.0):
+    def __init__(self, dim, heads, mlp_ratio=4, dropout=0.0, drop_path=0.0,
+                 attn_dropout=0.0):
         super().__init__()
         self.p, self.p_path = float(dropout), float(drop_path)
         self.norm1 = LayerNorm(dim)
-        self.attn = MultiHeadAttention(dim, heads)
+        self.attn = MultiHeadAttention(dim, heads, attn_dropout)
         self.norm2 = LayerNorm(dim)
         self.mlp = nn.Sequential(
             Linear(dim, dim * mlp_ratio),
@@ -105,6 +115,7 @@ class ViT(nn.Module):
         in_ch=3,
         dropout=0.0,
         drop_path=0.0,
+        attn_dropout=0.0,
     ):
         super().__init__()
         assert image_size % patch_size == 0
@@ -121,7 +132,7 @@ class ViT(nn.Module):
         # stochastic depth grows linearly from 0 (first block) to drop_path
         self.blocks = nn.Sequential(*[
             Block(dim, heads, mlp_ratio, dropout,
-                  drop_path * i / max(depth - 1, 1))
+                  drop_path * i / max(depth - 1, 1), attn_dropout)
             for i in range(depth)
         ])
         self.norm = LayerNorm(dim)
@@ -151,6 +162,8 @@ class ViT(nn.Module):
         return self.head(x[:, 0])
 
 
-def vit_b16(num_classes=1000, image_size=224, dropout=0.0, drop_path=0.0):
+def vit_b16(num_classes=1000, image_size=224, dropout=0.0, drop_path=0.0,
+            attn_dropout=0.0):
     return ViT(image_size=image_size, num_classes=num_classes,
-               dropout=dropout, drop_path=drop_path)
+               dropout=dropout, drop_path=drop_path,
+               attn_dropout=attn_dropout)

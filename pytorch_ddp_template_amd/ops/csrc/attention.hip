@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "dispatch.h"
+#include "philox.h"
 
 namespace attn {
 
@@ -421,13 +422,18 @@ constexpr int kBT = 64;  // backward q-tile and k-tile rows
 // + f32 stats: m[64], r[64], D[64]
 constexpr int kImg = kBT * kDh;
 
-template <typename T16>
-__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
+// DROP: the forward's dropout on the probabilities, regenerated from the same
+// (call id, step, key): with M = keep * s and P~ = P ∘ M,
+//   dV += P~^T dO,   dS = P ∘ (M ∘ dP - D) * scale,
+// D = rowsum(dO ∘ O) as before (O is the dropped output).  The keep bits are
+// drawn behind the S and dP MFMAs and live in one register.
+template <typename T16, bool DROP>
+DEV_INLINE void attn_bwd_body(
     const T16* __restrict__ qkv, const T16* __restrict__ dout,
     const float* __restrict__ stats, const float* __restrict__ Dsum,
     float* __restrict__ dq_partial, T16* __restrict__ dk,
     T16* __restrict__ dv, const T16* __restrict__ zpad, int N, int S, int H,
-    float scale) {
+    float scale, const rng::AttnDrop& drop) {
   __shared__ __attribute__((aligned(16))) char smem[9 * kImg * 2 + 3 * 64 * 4];
   T16* ldsKs = reinterpret_cast<T16*>(smem);
   T16* ldsKn = ldsKs + kImg;
@@ -536,6 +542,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
   const int qi = wave >> 1;   // q half for S/P/dS/dQ rows
   const int ki = wave & 1;    // k half for S/P/dS cols
 
+  uint32_t dstep = 0;
+  if constexpr (DROP) dstep = *drop.step;
+
   // ---- loop over q tiles ----
   for (int q0 = 0; q0 < S; q0 += kBT) {
     // stage Q (sw+nat), dO (sw+nat), stats/D rows
@@ -586,6 +595,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
       vec16 b = sw_frag(ldsVs, ki * 32 + r32, kc);
       accDP = MM<T16>::mma32(a, b, accDP);
     }
+    // the keep bits of this lane's quadrant column: integer VALU work that
+    // depends on neither product, so it runs while the MFMAs above drain
+    uint32_t keep = 0;
+    if constexpr (DROP)
+      keep = rng::attn_keep_bits(drop, dstep, (uint32_t)bh,
+                                 (uint32_t)(q0 / 32 + qi), (uint32_t)ks,
+                                 (uint32_t)S, (uint32_t)(k0 + ki * 32 + r32));
 
     // ---- P and dS in registers; P -> ldsPn (natural) ----
     const int colk = k0 + ki * 32 + r32;   // global k column of this lane
@@ -597,8 +613,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
       const float inv = stR[rowl];  // 0 for padded q rows
       float p = colk < S ? __expf(accS[r] * scale - m) * inv : 0.f;
       pr[r] = p;
-      dsr[r] = p * (accDP[r] - stD[rowl]) * scale;
-      ldsPn[rowl * kDh + ki * 32 + r32] = to_t<T16>(p);
+      if constexpr (DROP) {
+        dsr[r] = p * (rng::attn_keep(keep, r, accDP[r] * drop.scale) -
+                      stD[rowl]) * scale;
+        ldsPn[rowl * kDh + ki * 32 + r32] =
+            to_t<T16>(rng::attn_keep(keep, r, p * drop.scale));
+      } else {
+        dsr[r] = p * (accDP[r] - stD[rowl]) * scale;
+        ldsPn[rowl * kDh + ki * 32 + r32] = to_t<T16>(p);
+      }
     }
     __syncthreads();  // ldsPn complete
 
@@ -662,6 +685,28 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
 #undef LDSB
 }
 
+template <typename T16>
+__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
+    const T16* __restrict__ qkv, const T16* __restrict__ dout,
+    const float* __restrict__ stats, const float* __restrict__ Dsum,
+    float* __restrict__ dq_partial, T16* __restrict__ dk,
+    T16* __restrict__ dv, const T16* __restrict__ zpad, int N, int S, int H,
+    float scale) {
+  attn_bwd_body<T16, false>(qkv, dout, stats, Dsum, dq_partial, dk, dv, zpad,
+                            N, S, H, scale, rng::AttnDrop{});
+}
+
+template <typename T16>
+__global__ __launch_bounds__(256, 2) NO_PK_F32 void attn_bwd_drop_kernel(
+    const T16* __restrict__ qkv, const T16* __restrict__ dout,
+    const float* __restrict__ stats, const float* __restrict__ Dsum,
+    float* __restrict__ dq_partial, T16* __restrict__ dk,
+    T16* __restrict__ dv, const T16* __restrict__ zpad, int N, int S, int H,
+    float scale, rng::AttnDrop drop) {
+  attn_bwd_body<T16, true>(qkv, dout, stats, Dsum, dq_partial, dk, dv, zpad,
+                           N, S, H, scale, drop);
+}
+
 // ===================== flash-style attention FORWARD ======================
 //
 // The round-1 forward (attn_fwd_kernel above) gives one workgroup a whole
@@ -673,11 +718,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(
 // per k-tile.  Also removes the S <= 224 cap (K/V are tiled, not staged
 // whole) and writes the same stats the flash backward consumes.
 // Wave w owns the (w>>1, w&1) 32x32 quadrant of each 64x64 product.
-template <typename T16>
-__global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
+//
+// DROP: dropout on the probabilities (philox.h).  A lane's 16 accumulator
+// registers of a score quadrant are one Philox block, drawn behind the QK^T
+// MFMAs and kept as 16 bits in one register.  Only the P
+// tile that feeds PV is masked; the row sums and the saved stats stay those
+// of the undropped softmax (the backward recomputes P from them) and the keep
+// scale rides on the final 1/sum.
+template <typename T16, bool DROP>
+DEV_INLINE void attn_fwd_flash_body(
     const T16* __restrict__ qkv, T16* __restrict__ out,
     float* __restrict__ stats, const T16* __restrict__ zpad, int N, int S,
-    int H, float scale) {
+    int H, float scale, const rng::AttnDrop& drop) {
   __shared__ __attribute__((aligned(16))) char smem[4 * kImg * 2 +
                                                     2 * 128 * 4];
   T16* ldsQs = reinterpret_cast<T16*>(smem);
@@ -767,6 +819,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
     srow[r] = 0.f;
   }
 
+  uint32_t dstep = 0;
+  if constexpr (DROP) dstep = *drop.step;
   const int n_kt = (S + kBT - 1) / kBT;
   for (int kt = 0; kt < n_kt; ++kt) {
     __syncthreads();  // previous iteration's K/V/P readers done
@@ -797,6 +851,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
       vec16 b = sw_frag(ldsKs, ki * 32 + r32, kc);
       accS = MM<T16>::mma32(a, b, accS);
     }
+    // the keep bits of this lane's quadrant column: integer VALU work that
+    // does not depend on accS, so it runs while the MFMAs above drain
+    uint32_t keep = 0;
+    if constexpr (DROP)
+      keep = rng::attn_keep_bits(drop, dstep, (uint32_t)bh,
+                                 (uint32_t)(bx * 2 + qi), (uint32_t)ks,
+                                 (uint32_t)S, (uint32_t)(k0 + ki * 32 + r32));
 
     // ---- online softmax: per-row tile max within this ki half (32-lane
     // butterfly), cross-ki combine via LDS, exp + tile sums, rescale ----
@@ -830,7 +891,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
       if (r32 == 0) redS[rowl * 2 + ki] = s;  // this half's TILE sum
       // P tile into LDS (swizzled) for the PV A-operand
       const int c = ki * 32 + r32;
-      ldsPs[rowl * kDh + kqswz(c >> 3, rowl) + (c & 7)] = to_t<T16>(p);
+      ldsPs[rowl * kDh + kqswz(c >> 3, rowl) + (c & 7)] =
+          to_t<T16>(DROP ? rng::attn_keep(keep, r, p) : p);
     }
     __syncthreads();  // P + both sum halves visible
 #pragma unroll
@@ -856,13 +918,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
     if (row >= S) continue;
     const float inv = 1.f / srow[r];
     out[((long long)n * S + row) * D + hh * kDh + ki * 32 + r32] =
-        to_t<T16>(oacc[r] * inv);
+        to_t<T16>(oacc[r] * (DROP ? inv * drop.scale : inv));
     if (ki == 0 && r32 == 0) {
       stats[bh * S + row] = mrow[r];
       stats[((long long)N * H + bh) * S + row] = inv;
     }
   }
 #undef LDSB
+}
+
+template <typename T16>
+__global__ __launch_bounds__(256, 2) void attn_fwd_flash_kernel(
+    const T16* __restrict__ qkv, T16* __restrict__ out,
+    float* __restrict__ stats, const T16* __restrict__ zpad, int N, int S,
+    int H, float scale) {
+  attn_fwd_flash_body<T16, false>(qkv, out, stats, zpad, N, S, H, scale,
+                                  rng::AttnDrop{});
+}
+
+template <typename T16>
+__global__ __launch_bounds__(256, 2) NO_PK_F32 void attn_fwd_flash_drop_kernel(
+    const T16* __restrict__ qkv, T16* __restrict__ out,
+    float* __restrict__ stats, const T16* __restrict__ zpad, int N, int S,
+    int H, float scale, rng::AttnDrop drop) {
+  attn_fwd_flash_body<T16, true>(qkv, out, stats, zpad, N, S, H, scale, drop);
 }
 
 // D = rowsum(dO ∘ O) per (n, head, s) — one wave per (n, s, head) row.
@@ -1001,11 +1080,22 @@ __global__ void head_split_kernel(const T16* __restrict__ x,
 
 }  // namespace attn
 
+// dropout.hip: checks and packs the dropout arguments of a launch
+rng::AttnDrop attn_drop_args(const torch::Tensor& step, torch::Device dev,
+                             int64_t key0, int64_t key1, int64_t call_id,
+                             double p, long long B, long long S);
+
 // out[N,S,H*dh], P[N*H, S, S] (empty when !want_p), stats[2, N*H, S] f32.
 // want_p = true materializes P for the composed backward / A-B tests; the
 // production path uses want_p = false and the flash backward (attn_bwd).
+// p > 0: dropout on the probabilities inside the flash kernel, under the mask
+// of (call_id, step scalar, key0, key1) — see philox.h; attn_bwd takes the
+// same five values.
 std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads,
-                                    double scale, bool want_p) {
+                                    double scale, bool want_p,
+                                    c10::optional<torch::Tensor> step,
+                                    int64_t key0, int64_t key1,
+                                    int64_t call_id, double p) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(),
               "qkv must be [N, S, 3*H*dh] contiguous");
   const int N = (int)qkv.size(0), S = (int)qkv.size(1);
@@ -1018,6 +1108,15 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads,
   // two-pass kernel stages the whole K/V and is capped
   TORCH_CHECK(!want_p || S <= attn::kMaxSP,
               "S too large for the P-materializing kernel");
+  TORCH_CHECK(p >= 0.0, "attn_fwd: negative dropout rate ", p);
+  TORCH_CHECK(!(want_p && p > 0.0),
+              "attn_fwd: the P-materializing kernel has no dropout");
+  rng::AttnDrop drop{};
+  if (p > 0.0) {
+    TORCH_CHECK(step.has_value(), "attn_fwd: p > 0 needs the step scalar");
+    drop = attn_drop_args(*step, qkv.device(), key0, key1, call_id, p,
+                               (long long)N * H, S);
+  }
   auto out = torch::empty({N, S, (long long)H * dh}, qkv.options());
   auto P = want_p
                ? torch::empty({(long long)N * H, S, S}, qkv.options())
@@ -1030,7 +1129,16 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads,
   auto stream = c10::hip::getCurrentHIPStream();
   DDP_DISPATCH_FLOAT(qkv.scalar_type(), "attn_fwd", [&] {
     if constexpr (!std::is_same_v<scalar_t, float>) {
-      if (!want_p) {
+      if (p > 0.0) {
+        dim3 grid((unsigned)((S + attn::kBT - 1) / attn::kBT), H, N);
+        hipLaunchKernelGGL(
+            (attn::attn_fwd_flash_drop_kernel<scalar_t>), grid, dim3(256), 0,
+            stream, reinterpret_cast<const scalar_t*>(qkv.data_ptr()),
+            reinterpret_cast<scalar_t*>(out.data_ptr()),
+            stats.data_ptr<float>(),
+            reinterpret_cast<const scalar_t*>(zp.data_ptr()), N, S, H,
+            (float)scale, drop);
+      } else if (!want_p) {
         // flash forward: grid over 64-row q-tiles, online softmax, no P
         dim3 grid((unsigned)((S + attn::kBT - 1) / attn::kBT), H, N);
         hipLaunchKernelGGL((attn::attn_fwd_flash_kernel<scalar_t>), grid,
@@ -1062,7 +1170,8 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads,
 // tensors touch HBM; see attn_bwd_kernel.
 torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor dout,
                        torch::Tensor out, torch::Tensor stats, int64_t heads,
-                       double scale) {
+                       double scale, c10::optional<torch::Tensor> step,
+                       int64_t key0, int64_t key1, int64_t call_id, double p) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous());
   TORCH_CHECK(dout.is_contiguous() && out.is_contiguous());
   const int N = (int)qkv.size(0), S = (int)qkv.size(1);
@@ -1085,6 +1194,13 @@ torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor dout,
     zp = torch::zeros({64}, qkv.options());
   auto stream = c10::hip::getCurrentHIPStream();
   TORCH_CHECK(N <= 65535 && S <= 65535 && n_kt <= 65535);
+  TORCH_CHECK(p >= 0.0, "attn_bwd: negative dropout rate ", p);
+  rng::AttnDrop drop{};
+  if (p > 0.0) {
+    TORCH_CHECK(step.has_value(), "attn_bwd: p > 0 needs the step scalar");
+    drop = attn_drop_args(*step, qkv.device(), key0, key1, call_id, p, B,
+                               S);
+  }
   DDP_DISPATCH_FLOAT(qkv.scalar_type(), "attn_bwd", [&] {
     if constexpr (!std::is_same_v<scalar_t, float>) {
       const long long rows = (long long)N * S * H;
@@ -1094,16 +1210,30 @@ torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor dout,
                          reinterpret_cast<const scalar_t*>(dout.data_ptr()),
                          reinterpret_cast<const scalar_t*>(out.data_ptr()),
                          Dsum.data_ptr<float>(), N, S, H);
-      hipLaunchKernelGGL((attn::attn_bwd_kernel<scalar_t>),
-                         dim3(n_kt, H, N), dim3(256), 0, stream,
-                         reinterpret_cast<const scalar_t*>(qkv.data_ptr()),
-                         reinterpret_cast<const scalar_t*>(dout.data_ptr()),
-                         stats.data_ptr<float>(), Dsum.data_ptr<float>(),
-                         dq_partial.data_ptr<float>(),
-                         reinterpret_cast<scalar_t*>(dk.data_ptr()),
-                         reinterpret_cast<scalar_t*>(dv.data_ptr()),
-                         reinterpret_cast<const scalar_t*>(zp.data_ptr()), N,
-                         S, H, (float)scale);
+      if (p > 0.0) {
+        hipLaunchKernelGGL(
+            (attn::attn_bwd_drop_kernel<scalar_t>), dim3(n_kt, H, N),
+            dim3(256), 0, stream,
+            reinterpret_cast<const scalar_t*>(qkv.data_ptr()),
+            reinterpret_cast<const scalar_t*>(dout.data_ptr()),
+            stats.data_ptr<float>(), Dsum.data_ptr<float>(),
+            dq_partial.data_ptr<float>(),
+            reinterpret_cast<scalar_t*>(dk.data_ptr()),
+            reinterpret_cast<scalar_t*>(dv.data_ptr()),
+            reinterpret_cast<const scalar_t*>(zp.data_ptr()), N, S, H,
+            (float)scale, drop);
+      } else {
+        hipLaunchKernelGGL(
+            (attn::attn_bwd_kernel<scalar_t>), dim3(n_kt, H, N), dim3(256),
+            0, stream, reinterpret_cast<const scalar_t*>(qkv.data_ptr()),
+            reinterpret_cast<const scalar_t*>(dout.data_ptr()),
+            stats.data_ptr<float>(), Dsum.data_ptr<float>(),
+            dq_partial.data_ptr<float>(),
+            reinterpret_cast<scalar_t*>(dk.data_ptr()),
+            reinterpret_cast<scalar_t*>(dv.data_ptr()),
+            reinterpret_cast<const scalar_t*>(zp.data_ptr()), N, S, H,
+            (float)scale);
+      }
       dim3 pgrid((unsigned)((3 * H * (attn::kDh / 8) + 255) / 256),
                  (unsigned)S, (unsigned)N);
       hipLaunchKernelGGL((attn::qkv_pack_flash_kernel<scalar_t>), pgrid,

@@ -30,38 +30,15 @@
 
 #include "common.h"
 #include "dispatch.h"
+#include "philox.h"
 
 namespace dp {
 
 constexpr int kBlock = 256;
 constexpr int kGridCap = 2048;
 
-constexpr uint32_t kMul0 = 0xD2511F53u, kMul1 = 0xCD9E8D57u;
-constexpr uint32_t kWeyl0 = 0x9E3779B9u, kWeyl1 = 0xBB67AE85u;
-
-struct U4 {
-  uint32_t w0, w1, w2, w3;
-};
-
-// Philox4x32-10.  The two 32x32 -> 64 products per round are plain C++; the
-// compiler picks the multiply instructions.
-DEV_INLINE U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                     uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)kMul0 * c0;
-    const uint64_t p1 = (uint64_t)kMul1 * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += kWeyl0;
-    k1 += kWeyl1;
-  }
-  return {c0, c1, c2, c3};
-}
+using rng::philox;
+using rng::U4;
 
 // word (i & 3) without indexing a register array
 DEV_INLINE uint32_t pick(const U4& v, unsigned i) {
@@ -175,6 +152,34 @@ __global__ void dropout_kernel(const T* __restrict__ x,
   }
 }
 
+// The attention keep mask (philox.h) on materialised probabilities
+// x [B, S, S]: out = keep ? x * scale : 0.  This is the composed attention
+// route's dropout (fp32, head sizes other than 64), not a hot path; the fused
+// kernels of attention.hip draw the same mask in registers.  One thread per
+// Philox block: 16 rows of one column, so a wave's stores of one row are
+// contiguous.  Backward is the same kernel on dP.
+template <typename T>
+__global__ NO_PK_F32 void attn_dropout_kernel(const T* __restrict__ x,
+                                              T* __restrict__ out,
+                                              rng::AttnDrop d, uint32_t S,
+                                              long long nblk) {
+  const uint32_t step = *d.step;
+  GRID_STRIDE(i, nblk) {
+    // i = ((bh * nq32 + q32) * 2 + ks) * S + k, all below 2^32 (host check)
+    const uint32_t t = (uint32_t)i / S, k = (uint32_t)i - t * S;
+    const uint32_t ks = t & 1u, u = t >> 1;
+    const uint32_t bh = u / d.nq32, q32 = u - bh * d.nq32;
+    const uint32_t bits = rng::attn_keep_bits(d, step, bh, q32, ks, S, k);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t row = q32 * 32 + (j & 3) + 8 * (j >> 2) + 4 * ks;
+      if (row >= S) continue;
+      const long long e = ((long long)bh * S + row) * S + k;
+      out[e] = to_t<T>(rng::attn_keep(bits, j, to_f(x[e]) * d.scale));
+    }
+  }
+}
+
 }  // namespace dp
 
 // ======================= host launcher ===================================
@@ -279,6 +284,62 @@ torch::Tensor dropout_fwd(torch::Tensor x, c10::optional<torch::Tensor> res,
   const torch::Tensor* rp = res.has_value() ? &*res : nullptr;
   DDP_DISPATCH_FLOAT(x.scalar_type(), "dropout_fwd", [&] {
     route<scalar_t>(p_elem > 0.0, row, x, rp, out, step, p);
+  });
+  return out;
+}
+
+// The kernel argument of the attention mask (philox.h) for rate p on
+// B x S x S probabilities held on `dev`; `step` is the one-element int32
+// device scalar of ops/rng.py.  Also called by attn_fwd / attn_bwd
+// (attention.hip).
+rng::AttnDrop attn_drop_args(const torch::Tensor& step, torch::Device dev,
+                             int64_t key0, int64_t key1, int64_t call_id,
+                             double p, long long B, long long S) {
+  TORCH_CHECK(step.is_cuda() && step.numel() == 1 &&
+                  step.scalar_type() == torch::kInt32 && step.device() == dev,
+              "attention dropout: step must be a one-element int32 tensor on "
+              "the input's device");
+  TORCH_CHECK(p > 0.0 && p < 1.0, "attention dropout: rate ", p,
+              " not in (0, 1)");
+  const uint32_t thr8 = (uint32_t)std::floor(p * 256.0);
+  TORCH_CHECK(thr8 >= 1, "attention dropout: rate ", p,
+              " is below 1/256 and would drop nothing");
+  const long long nq32 = (S + 31) / 32;
+  TORCH_CHECK(B * nq32 * 2 * S <= 0xffffffffLL,
+              "attention dropout: the block counter of ", B, " x ", S, " x ",
+              S, " probabilities does not fit 32 bits");
+  rng::AttnDrop d;
+  d.step = reinterpret_cast<const uint32_t*>(step.data_ptr());
+  d.key0 = (uint32_t)key0;
+  d.key1 = (uint32_t)key1;
+  d.cid_lo = (uint32_t)((uint64_t)call_id & 0xffffffffu);
+  d.cid_hi = (uint32_t)((uint64_t)call_id >> 32);
+  d.thr8 = thr8;
+  d.nq32 = (uint32_t)nq32;
+  d.scale = (float)(256.0 / (256.0 - (double)thr8));
+  return d;
+}
+
+// x [B, S, S] contiguous probabilities (or their gradient); returns
+// keep ? x * scale : 0 under the attention mask of (call_id, step, key).
+torch::Tensor attn_dropout(torch::Tensor x, torch::Tensor step, int64_t key0,
+                           int64_t key1, int64_t call_id, double p) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3 &&
+                  x.size(1) == x.size(2),
+              "attn_dropout: x must be [B, S, S] contiguous GPU");
+  const long long B = x.size(0), S = x.size(1);
+  auto out = torch::empty_like(x);
+  if (x.numel() == 0) return out;
+  const rng::AttnDrop d =
+      attn_drop_args(step, x.device(), key0, key1, call_id, p, B, S);
+  const long long nblk = B * d.nq32 * 2 * S;
+  const int blocks = grid_1d(nblk, dp::kBlock, dp::kGridCap);
+  DDP_DISPATCH_FLOAT(x.scalar_type(), "attn_dropout", [&] {
+    hipLaunchKernelGGL((dp::attn_dropout_kernel<scalar_t>), dim3(blocks),
+                       dim3(dp::kBlock), 0, c10::hip::getCurrentHIPStream(),
+                       reinterpret_cast<const scalar_t*>(x.data_ptr()),
+                       reinterpret_cast<scalar_t*>(out.data_ptr()), d,
+                       (uint32_t)S, nblk);
   });
   return out;
 }

@@ -124,11 +124,16 @@ std::vector<torch::Tensor> qkv_unpack(torch::Tensor qkv, int64_t heads);
 torch::Tensor qkv_pack(torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                        int64_t N, int64_t heads);
 torch::Tensor head_split(torch::Tensor x, int64_t heads);
+// (step, key0, key1, call_id, p): dropout on the probabilities; p == 0: off
 std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads,
-                                    double scale, bool want_p);
+                                    double scale, bool want_p,
+                                    c10::optional<torch::Tensor> step,
+                                    int64_t key0, int64_t key1,
+                                    int64_t call_id, double p);
 torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor dout,
                        torch::Tensor out, torch::Tensor stats, int64_t heads,
-                       double scale);
+                       double scale, c10::optional<torch::Tensor> step,
+                       int64_t key0, int64_t key1, int64_t call_id, double p);
 // multi_tensor.hip
 void sgd_step(std::vector<torch::Tensor> params,
               std::vector<torch::Tensor> grads,
@@ -156,6 +161,9 @@ torch::Tensor dropout_fwd(torch::Tensor x, c10::optional<torch::Tensor> res,
                           int64_t key0, int64_t key1, int64_t call_id_elem,
                           int64_t call_id_row, double p_elem, double p_row,
                           int64_t inner);
+// dropout.hip: the attention keep mask on materialised [B, S, S] probabilities
+torch::Tensor attn_dropout(torch::Tensor x, torch::Tensor step, int64_t key0,
+                           int64_t key1, int64_t call_id, double p);
 int64_t dropout_grid_cap();
 int64_t dropout_block();
 
@@ -410,8 +418,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("softmax_fwd", &softmax_fwd);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"),
-        py::arg("scale"), py::arg("want_p") = false);
-  m.def("attn_bwd", &attn_bwd);
+        py::arg("scale"), py::arg("want_p") = false,
+        py::arg("step") = c10::nullopt, py::arg("key0") = 0,
+        py::arg("key1") = 0, py::arg("call_id") = 0, py::arg("p") = 0.0);
+  m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("dout"),
+        py::arg("out"), py::arg("stats"), py::arg("heads"), py::arg("scale"),
+        py::arg("step") = c10::nullopt, py::arg("key0") = 0,
+        py::arg("key1") = 0, py::arg("call_id") = 0, py::arg("p") = 0.0);
+  m.def("attn_dropout", &attn_dropout, py::arg("x"), py::arg("step"),
+        py::arg("key0"), py::arg("key1"), py::arg("call_id"), py::arg("p"));
   m.def("qkv_unpack", &qkv_unpack);
   m.def("qkv_pack", &qkv_pack);
   m.def("head_split", &head_split);

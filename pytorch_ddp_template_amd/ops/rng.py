@@ -25,6 +25,26 @@ capture use smaller or larger ids than the captured ones.
 
 The numpy implementation below is the CPU path of ``ops.functional.dropout*``
 and produces the same bits as ``ops/csrc/dropout.hip``.
+
+**Attention-probability mask** (``attention`` / ``attention_qkv`` with
+``p > 0``).  A word per element would cost the fused attention kernels four
+Philox blocks per lane and 64x64 tile pair, so this mask spends one *byte* per
+element.  Element ``(bh, q, k)`` of the ``[B, S, S]`` probabilities, with
+``rho = q & 31``, ``ks = (rho >> 2) & 1`` and ``j = (rho & 3) + 4 * (rho >> 3)``,
+draws byte ``j & 3`` (little-endian) of output word ``j >> 2`` of the block
+whose counter is::
+
+    (((bh * ceil(S / 32) + (q >> 5)) * 2 + ks) * S + k,
+     call_id & 0xFFFFFFFF, call_id >> 32, step)
+
+under the same key.  It is kept iff ``byte >= thr8 = floor(p * 256)`` and
+scaled by ``float32(256 / (256 - thr8))``, the reciprocal of the *effective*
+keep rate, so the expectation is exact; ``0 < p < 1/256`` would drop nothing
+and is an error.  ``(ks, j)`` is the (lane half, register) that holds row
+``rho`` of a 32x32 ``mfma_f32_32x32x16`` accumulator, so one lane of a score
+quadrant owns exactly one block; the map depends on ``(bh, q, k)`` alone, and
+the fused forward, the fused backward, the composed GPU route
+(``ops/csrc/philox.h``) and :func:`attn_keep_mask` all use it.
 """
 
 from __future__ import annotations
@@ -169,3 +189,59 @@ def keep_mask(n: int, p: float, call_id: int, step: int) -> torch.Tensor:
     """Bool tensor [n]: element kept iff its word >= floor(p * 2^32)."""
     w = draws(n, call_id, step)
     return torch.from_numpy(w >= np.uint64(keep_threshold(p)))
+
+
+# ------------------------------------------- attention-probability mask ----
+
+
+def attn_keep_threshold(p: float) -> int:
+    """thr8 = floor(p * 256); a rate in (0, 1/256) would drop nothing."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout rate must be in [0, 1), got {p}")
+    thr8 = int(math.floor(p * 256.0))
+    if p > 0 and thr8 == 0:
+        raise ValueError(
+            f"attention dropout rate {p} is below 1/256: the byte mask would "
+            "drop nothing")
+    return thr8
+
+
+def attn_keep_scale(p: float) -> float:
+    """float32(256 / (256 - thr8)): one over the effective keep rate."""
+    return float(np.float32(256.0 / (256.0 - attn_keep_threshold(p))))
+
+
+def attn_draw_index(B: int, S: int) -> tuple[np.ndarray, np.ndarray]:
+    """(counter word 0, byte index 0..15) of every element, each [B, S, S]."""
+    nq32 = (S + 31) // 32
+    if B * nq32 * 2 * S > _MASK32:
+        raise ValueError(
+            f"attention dropout: the block counter of {B} x {S} x {S} "
+            "probabilities does not fit 32 bits")
+    bh = np.arange(B, dtype=np.uint64)[:, None, None]
+    q = np.arange(S, dtype=np.uint64)[None, :, None]
+    k = np.arange(S, dtype=np.uint64)[None, None, :]
+    rho = q & np.uint64(31)
+    ks = (rho >> np.uint64(2)) & np.uint64(1)
+    j = (rho & np.uint64(3)) + np.uint64(4) * (rho >> np.uint64(3))
+    c0 = ((bh * np.uint64(nq32) + (q >> np.uint64(5))) * np.uint64(2)
+          + ks) * np.uint64(S) + k
+    return c0, np.broadcast_to(j, c0.shape)
+
+
+def attn_keep_mask(B: int, S: int, p: float, call_id: int,
+                   step: int) -> torch.Tensor:
+    """Bool tensor [B, S, S]: the attention-probability keep mask of a call
+    under the current key (module docstring)."""
+    thr8 = attn_keep_threshold(p)
+    c0, j = attn_draw_index(B, S)
+    k0, k1 = key()
+    # the counters are 0 .. B * ceil(S/32) * 2 * S - 1: draw each block once
+    blocks = np.arange(B * ((S + 31) // 32) * 2 * S, dtype=np.uint64)
+    w = np.stack(philox4x32_10(blocks, call_id & _MASK32,
+                               (call_id >> 32) & _MASK32, step & _MASK32,
+                               k0, k1), axis=1)
+    word = w[c0.astype(np.intp), (j >> np.uint64(2)).astype(np.intp)]
+    byte = (word >> (np.uint64(8) * (j & np.uint64(3)))) & np.uint64(0xFF)
+    return torch.from_numpy(byte >= np.uint64(thr8))
