@@ -50,7 +50,7 @@ from .optim import (
     param_groups_no_decay,
 )
 from .ops import scale_grads_
-from .ops import CrossEntropyLoss, MSELoss
+from .ops import BatchMix, CrossEntropyLoss, MSELoss
 from .ops import rng as philox_rng
 from .parallel import DistributedModel
 from .utils import (
@@ -334,9 +334,11 @@ class GraphStep:
 
     WARMUP = 3
 
-    def __init__(self, model, criterion, optimizer, max_grad_norm):
+    def __init__(self, model, criterion, optimizer, max_grad_norm,
+                 batch_mix=None):
         self.model, self.criterion = model, criterion
         self.optimizer, self.max_grad_norm = optimizer, max_grad_norm
+        self.batch_mix = batch_mix
         self.side = torch.cuda.Stream()
         self.graph = None
         self.loss_st = None
@@ -349,6 +351,10 @@ class GraphStep:
         # call ids baked into the graph (3 warm-ups + 1 capture pass that only
         # records + N replays leave the scalar at 3 + N)
         philox_rng.tick(self.x_st.device)
+        if self.batch_mix is not None:
+            # drawn on the device from the ticked step: a replay mixes the
+            # refreshed x_st with a fresh lambda and box
+            self.batch_mix.apply_(self.x_st)
         out = self.model(self.x_st)
         loss = self.criterion(out, self.y_st)
         loss.backward()
@@ -389,10 +395,19 @@ class GraphStep:
         return self.loss_st.detach()
 
 
-def _criterion_for(args):
+def _criterion_for(args, train=True):
+    """train: the criterion of --label_smoothing / --mixup / --cutmix (its
+    ``mix`` is the BatchMix the train loop applies to every micro-batch);
+    with those flags at their defaults, and for evaluation, the plain one."""
     if args.model in ("foo", "foomodel", "mlp"):
         return MSELoss()  # reference ddp.py:164
-    return CrossEntropyLoss()
+    if not train:
+        return CrossEntropyLoss()
+    mix = None
+    if getattr(args, "mixup", 0.0) or getattr(args, "cutmix", 0.0):
+        mix = BatchMix(args.mixup, args.cutmix, args.mix_prob,
+                       args.mix_switch_prob)
+    return CrossEntropyLoss(getattr(args, "label_smoothing", 0.0), mix)
 
 
 def _cast_model(args, model):
@@ -431,7 +446,7 @@ def evaluate(args, model, dataset=None, max_batches=None):
         batch_size=args.train_batch_size,
         pin_memory=args.device.type == "cuda",
     )
-    criterion = _criterion_for(args)
+    criterion = _criterion_for(args, train=False)
     model.eval()
     # [loss_sum (sample-weighted), n_samples, n_correct] — one all-reduce
     totals = torch.zeros(3, dtype=torch.float64)
@@ -531,7 +546,8 @@ def train(args, model):
             len(loader) // args.gradient_accumulation_steps * args.num_train_epochs
         )
 
-    criterion = _criterion_for(args)
+    criterion = _criterion_for(args, train=True)
+    batch_mix = getattr(criterion, "mix", None)
     use_master = args.bf16 or args.fp16
     if args.optimizer == "adamw":
         optimizer = AdamW(
@@ -610,7 +626,8 @@ def train(args, model):
         and args.gradient_accumulation_steps == 1
         and scaler is None
     ):
-        graph_step = GraphStep(model, criterion, optimizer, args.max_grad_norm)
+        graph_step = GraphStep(model, criterion, optimizer, args.max_grad_norm,
+                               batch_mix)
     elif args.hip_graph and is_main_process():
         logger.warning(
             "--hip_graph ignored (needs single-process CUDA, accumulation=1,"
@@ -686,6 +703,8 @@ def train(args, model):
                 global_step += 1
             else:
               with sync_ctx:
+                if batch_mix is not None:
+                    batch_mix.apply_(x)
                 outputs = model(x)
                 loss = criterion(outputs, y)
                 if args.gradient_accumulation_steps > 1:
@@ -854,6 +873,20 @@ def build_parser():
                         help="ViT dropout rate on the attention probabilities "
                              "(inside the fused attention kernels); 0 or at "
                              "least 1/256")
+    parser.add_argument("--label_smoothing", type=float, default=0.0,
+                        help="weight of the uniform distribution in the "
+                             "training target (classification models)")
+    parser.add_argument("--mixup", type=float, default=0.0,
+                        help="mixup alpha, lambda ~ Beta(alpha, alpha) drawn "
+                             "on the device once per micro-batch; 0 = off, "
+                             "at most 1")
+    parser.add_argument("--cutmix", type=float, default=0.0,
+                        help="cutmix alpha; 0 = off, at most 1")
+    parser.add_argument("--mix_prob", type=float, default=1.0,
+                        help="chance that a micro-batch is mixed at all")
+    parser.add_argument("--mix_switch_prob", type=float, default=0.5,
+                        help="chance of cutmix when --mixup and --cutmix are "
+                             "both on")
     parser.add_argument("--bf16", action="store_true",
                         help="bf16 weights/activations with fp32 master weights")
     parser.add_argument("--resume_from", type=str, default=None)
@@ -892,6 +925,23 @@ def main(argv=None):
     if 0.0 < args.attn_dropout < 1.0 / 256.0:
         parser.error("--attn_dropout below 1/256 would drop nothing "
                      f"(one byte per element), got {args.attn_dropout}")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        parser.error("--label_smoothing must be in [0, 1), got "
+                     f"{args.label_smoothing}")
+    for flag in ("mixup", "cutmix"):
+        alpha = getattr(args, flag)
+        if not 0.0 <= alpha <= 1.0:
+            parser.error(f"--{flag} must be in [0, 1], got {alpha}: lambda is "
+                         "drawn by a one-wave Beta sampler that needs "
+                         "alpha <= 1")
+    for flag in ("mix_prob", "mix_switch_prob"):
+        if not 0.0 <= getattr(args, flag) <= 1.0:
+            parser.error(f"--{flag} must be in [0, 1], got "
+                         f"{getattr(args, flag)}")
+    for flag in ("label_smoothing", "mixup", "cutmix"):
+        if getattr(args, flag) and args.model in ("foo", "foomodel", "mlp"):
+            parser.error(f"--{flag} needs a classification model, "
+                         f"not --model {args.model}")
     if args.dataset is None:
         args.dataset = args.model
     setup(args)

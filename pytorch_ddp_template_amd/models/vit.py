@@ -25,8 +25,9 @@ the fused route it happens inside the flash forward and backward kernels (the
 probabilities never exist in memory; both kernels regenerate the mask); the
 composed route applies the same mask to the materialized probabilities.
 
-Not covered: fusing the post-GELU dropout into the GELU kernel, label
-smoothing.
+Not covered: fusing the post-GELU dropout into the GELU kernel.  (Label
+smoothing and mixup / cutmix live outside the model: ``ops.BatchMix`` and
+``ops.CrossEntropyLoss``.)
 """
 
 from __future__ import annotations

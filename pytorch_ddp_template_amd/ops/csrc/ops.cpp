@@ -119,6 +119,24 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
                      torch::Tensor lse, torch::Tensor dloss);
 torch::Tensor mse_fwd(torch::Tensor p, torch::Tensor t);
 torch::Tensor mse_bwd(torch::Tensor p, torch::Tensor t, torch::Tensor dloss);
+// loss.hip: soft-target CE (label smoothing eps; mixed labels under the mix
+// params record of mix.hip, None: own label only)
+std::vector<torch::Tensor> ce_soft_fwd(torch::Tensor logits,
+                                       torch::Tensor target, double eps,
+                                       c10::optional<torch::Tensor> mix);
+torch::Tensor ce_soft_bwd(torch::Tensor logits, torch::Tensor target,
+                          torch::Tensor lse, torch::Tensor dloss, double eps,
+                          c10::optional<torch::Tensor> mix);
+// mix.hip: mixup / cutmix parameters drawn on the device into the 8-slot
+// record, and the in-place batch mix that reads them
+void mix_draw(torch::Tensor rec, torch::Tensor step, int64_t key0,
+              int64_t key1, int64_t call_id, int64_t H, int64_t W,
+              double alpha_mix, double alpha_cut, double prob,
+              double switch_prob);
+torch::Tensor mix_batch_(torch::Tensor x, torch::Tensor rec, int64_t H,
+                         int64_t W, int64_t xmul);
+int64_t mix_grid_cap();
+int64_t mix_block();
 // attention.hip
 std::vector<torch::Tensor> qkv_unpack(torch::Tensor qkv, int64_t heads);
 torch::Tensor qkv_pack(torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
@@ -435,6 +453,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("mse_fwd", &mse_fwd);
   m.def("mse_bwd", &mse_bwd);
+  m.def("ce_soft_fwd", &ce_soft_fwd, py::arg("logits"), py::arg("target"),
+        py::arg("eps"), py::arg("mix") = c10::nullopt);
+  m.def("ce_soft_bwd", &ce_soft_bwd, py::arg("logits"), py::arg("target"),
+        py::arg("lse"), py::arg("dloss"), py::arg("eps"),
+        py::arg("mix") = c10::nullopt);
+  m.def("mix_draw", &mix_draw, py::arg("rec"), py::arg("step"),
+        py::arg("key0"), py::arg("key1"), py::arg("call_id"), py::arg("H"),
+        py::arg("W"), py::arg("alpha_mix"), py::arg("alpha_cut"),
+        py::arg("prob"), py::arg("switch_prob"));
+  m.def("mix_batch_", &mix_batch_, py::arg("x"), py::arg("rec"), py::arg("H"),
+        py::arg("W"), py::arg("xmul"));
+  m.def("mix_grid_cap", &mix_grid_cap);
+  m.def("mix_block", &mix_block);
   m.def("sgd_step", &sgd_step, py::arg("params"), py::arg("grads"),
         py::arg("moms"), py::arg("masters"), py::arg("lr"),
         py::arg("momentum"), py::arg("wd"), py::arg("damp"),

@@ -448,8 +448,102 @@ class _CrossEntropyFn(torch.autograd.Function):
         return dl, None
 
 
-def cross_entropy(logits, target):
-    return _CrossEntropyFn.apply(logits, target)
+def _mix_params(mix, device):
+    """The 8-slot record of a BatchMix (or the tensor itself) on device."""
+    if mix is None or isinstance(mix, torch.Tensor):
+        return mix
+    return mix.params(device)
+
+
+class _SoftCrossEntropyFn(torch.autograd.Function):
+    """Cross-entropy against the soft target
+    q_d = eps/D + (1-eps) (lam [d == t_m] + (1-lam) [d == t_{M-1-m}]),
+    mean reduction.  lam is slot 0 of the mix params record (None: 1), read on
+    the device by both kernels; q is never built on the GPU.  Forward and
+    backward see the same record: only the next step's draw writes it."""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps, params):
+        if use_native(logits):
+            loss, lse = native().ce_soft_fwd(
+                logits.contiguous(), target.contiguous(), eps, params)
+        else:
+            lf = logits.float()
+            lse = torch.logsumexp(lf, dim=1)
+            q = _soft_target(lf, target, eps, params)
+            loss = (lse - (q * lf).sum(1)).mean()
+        ctx.save_for_backward(logits, target, lse)
+        ctx.eps, ctx.params = eps, params
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, lse = ctx.saved_tensors
+        if use_native(logits):
+            dl = native().ce_soft_bwd(
+                logits.contiguous(), target.contiguous(), lse,
+                dloss.to(logits.device), ctx.eps, ctx.params)
+        else:
+            lf = logits.float()
+            q = _soft_target(lf, target, ctx.eps, ctx.params)
+            scale = float(dloss) / logits.shape[0]
+            dl = ((torch.softmax(lf, dim=1) - q) * scale).to(logits.dtype)
+        return dl, None, None, None
+
+
+def _soft_target(lf, target, eps, params):
+    """CPU path: the [M, D] float32 soft target."""
+    lam = 1.0 if params is None else float(params[0])
+    D = lf.shape[1]
+    onehot = F.one_hot(target, D).float()
+    q = lam * onehot + (1.0 - lam) * onehot.flip(0)
+    return eps / D + (1.0 - eps) * q
+
+
+def cross_entropy(logits, target, label_smoothing=0.0, mix=None):
+    """Mean cross-entropy of [M, D] logits against int64 targets [M].
+
+    label_smoothing: weight eps of the uniform distribution in the target.
+    mix: a ``BatchMix`` (or its params tensor) whose last draw mixed the batch;
+    row m's target is then lam of its own label plus (1 - lam) of the label of
+    row M-1-m.  With the defaults this is the hard-label kernel pair."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(
+            f"label_smoothing must be in [0, 1), got {label_smoothing}")
+    if label_smoothing == 0 and mix is None:
+        return _CrossEntropyFn.apply(logits, target)
+    return _SoftCrossEntropyFn.apply(
+        logits, target, float(label_smoothing),
+        _mix_params(mix, logits.device))
+
+
+def batch_mix_(x, mix):
+    """Mix the image batch x in place under the record of ``mix`` (a
+    ``BatchMix`` or its params tensor): sample i takes the box of, or blends
+    with, sample B-1-i.  x: contiguous 4-D, NHWC or (3 channels first) NCHW,
+    told apart as the models do."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("batch_mix_: x must be a contiguous 4-D image batch")
+    params = _mix_params(mix, x.device)
+    nchw = x.shape[1] == 3 and x.shape[-1] != 3
+    H, W = (x.shape[2], x.shape[3]) if nchw else (x.shape[1], x.shape[2])
+    if use_native(x):
+        return native().mix_batch_(x, params, H, W, 1 if nchw else x.shape[3])
+    ints = params.view(torch.int32)
+    if int(ints[6]) == rng.MIX_NONE:
+        return x
+    a = float(params[1])
+    y0, y1, x0, x1 = (int(v) for v in ints[2:6])
+    xp = x.flip(0)
+    out = x.clone() if a == 1.0 else (
+        a * x.float() + (1.0 - a) * xp.float()).to(x.dtype)
+    box = (slice(None), slice(None), slice(y0, y1), slice(x0, x1)) if nchw \
+        else (slice(None), slice(y0, y1), slice(x0, x1))
+    out[box] = xp[box]
+    B = x.shape[0]
+    if B % 2:
+        out[B // 2] = x[B // 2]
+    return x.copy_(out)
 
 
 class _MSEFn(torch.autograd.Function):

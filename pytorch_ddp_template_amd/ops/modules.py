@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from . import functional as X
+from . import rng
 
 
 class Linear(nn.Module):
@@ -206,7 +207,88 @@ class MSELoss(nn.Module):
 
 
 class CrossEntropyLoss(nn.Module):
-    """Fused log-softmax + NLL, mean reduction."""
+    """Fused log-softmax + NLL, mean reduction.
+
+    label_smoothing / mix (a :class:`BatchMix`) switch to the soft-target
+    kernels, in train mode only; eval mode and the argument-free form are the
+    hard-label loss."""
+
+    def __init__(self, label_smoothing=0.0, mix=None):
+        super().__init__()
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(
+                f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.label_smoothing = float(label_smoothing)
+        self.mix = mix
 
     def forward(self, logits, target):
-        return X.cross_entropy(logits, target)
+        if not self.training:
+            return X.cross_entropy(logits, target)
+        return X.cross_entropy(logits, target, self.label_smoothing, self.mix)
+
+    def extra_repr(self):
+        return f"label_smoothing={self.label_smoothing}, mix={self.mix}"
+
+
+class BatchMix:
+    """Mixup / cutmix of an image batch with its flip (sample i with B-1-i).
+
+    One draw per call: lambda ~ Beta(alpha, alpha), the choice between the two
+    modes and the cutmix box all come from the counter-based generator of
+    ``ops/rng.py`` and are drawn ON THE DEVICE into the params record, which
+    the mix kernel and the loss (``CrossEntropyLoss(mix=self)``) read there.  A
+    captured step therefore mixes differently on every replay.  Not an
+    nn.Module: it holds no weights and nothing for a checkpoint.
+
+    mixup_alpha / cutmix_alpha: 0 switches that mode off; at most 1 (the
+    wave-wide Beta sampler's limit).  prob: chance that a batch is mixed at
+    all; switch_prob: chance of cutmix when both modes are on."""
+
+    def __init__(self, mixup_alpha, cutmix_alpha, prob=1.0, switch_prob=0.5):
+        rng.check_mix_args(mixup_alpha, cutmix_alpha, prob, switch_prob)
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        self._params = {}
+
+    def params(self, device) -> torch.Tensor:
+        """The device's record (8 four-byte slots, see ``rng.mix_record``),
+        created on first use as "not applied" and never reallocated."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._params.get(device)
+        if t is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(
+                    "BatchMix.params: the params record of a device must "
+                    "exist before a stream capture begins (run one eager "
+                    "step, or call params(device) first)"
+                )
+            t = self._params[device] = rng.mix_record().to(device)
+        return t
+
+    def apply_(self, x):
+        """Draw this call's parameters and mix x in place; returns x."""
+        if x.dim() != 4:
+            raise ValueError("BatchMix.apply_: x must be a 4-D image batch")
+        nchw = x.shape[1] == 3 and x.shape[-1] != 3  # the models' rule
+        H, W = (x.shape[2], x.shape[3]) if nchw else (x.shape[1], x.shape[2])
+        params = self.params(x.device)
+        step = rng.step_scalar(x.device)
+        cid = rng.next_call_id()
+        args = (H, W, self.mixup_alpha, self.cutmix_alpha, self.prob,
+                self.switch_prob)
+        if X.use_native(x):
+            k0, k1 = rng.key()
+            X.native().mix_draw(params, step, k0, k1, cid, *args)
+        else:
+            d = rng.mix_draw(*args, cid, int(step.item()))
+            params.copy_(rng.mix_record(
+                d["lam"], d["a"], (d["y0"], d["y1"], d["x0"], d["x1"]),
+                d["mode"], d["raw"]))
+        return X.batch_mix_(x, params)
+
+    def __repr__(self):
+        return (f"BatchMix(mixup_alpha={self.mixup_alpha}, cutmix_alpha="
+                f"{self.cutmix_alpha}, prob={self.prob}, switch_prob="
+                f"{self.switch_prob})")

@@ -45,6 +45,30 @@ and is an error.  ``(ks, j)`` is the (lane half, register) that holds row
 quadrant owns exactly one block; the map depends on ``(bh, q, k)`` alone, and
 the fused forward, the fused backward, the composed GPU route
 (``ops/csrc/philox.h``) and :func:`attn_keep_mask` all use it.
+
+**Mixup / cutmix parameters** (``BatchMix``, ``ops/csrc/mix.hip``).  One draw
+per micro-batch takes one ``call_id`` and uses 65 blocks with counters
+``(c0, call_id & 0xFFFFFFFF, call_id >> 32, step)`` under the same key:
+
+* ``c0 = 64``, the choice block: apply iff ``w0 < floor(prob * 2^32)``; cutmix
+  rather than mixup iff ``w1 < floor(switch_prob * 2^32)`` (with only one
+  alpha nonzero that mode is always chosen); box centre ``cy = w2 mod H``,
+  ``cx = w3 mod W``.
+* ``c0 = t`` for ``t = 0..63``, try ``t`` of Jöhnk's sampler for
+  ``Beta(alpha, alpha)``, ``0 < alpha <= 1``: ``U = (w0 + 0.5) * 2^-32``,
+  ``V = (w1 + 0.5) * 2^-32``, ``X = U^(1/alpha)``, ``Y = V^(1/alpha)``; the try
+  accepts iff ``X + Y <= 1``.  The lowest accepting try wins and ``lambda =
+  X / (X + Y)`` (on the GPU the 64 tries are the 64 lanes of one wave); if
+  none accepts, ``lambda = 0.5`` (probability at most 2^-64).
+
+Cutmix cuts timm's box: ``r = sqrt(1 - lambda)``, ``ch = int(H r)``, ``cw =
+int(W r)``, ``y0, y1 = clamp(cy -+ ch // 2, 0, H)`` and likewise in x, and the
+label weight becomes ``(H W - box area) / (H W)`` rounded once to float32.
+The forward and the backward of the loss read that weight from the record the
+draw wrote; the only thing that writes the record is the next step's draw,
+which runs before that step's forward, so both always see the same values.
+:func:`mix_draw` is the float64 mirror of the kernel: the CPU path and the
+oracle of the GPU draw.
 """
 
 from __future__ import annotations
@@ -245,3 +269,107 @@ def attn_keep_mask(B: int, S: int, p: float, call_id: int,
     word = w[c0.astype(np.intp), (j >> np.uint64(2)).astype(np.intp)]
     byte = (word >> (np.uint64(8) * (j & np.uint64(3)))) & np.uint64(0xFF)
     return torch.from_numpy(byte >= np.uint64(thr8))
+
+
+# ------------------------------------------------ mixup / cutmix draw -------
+
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+def check_mix_args(alpha_mix, alpha_cut, prob=1.0, switch_prob=0.5) -> None:
+    """The argument rules of the draw (module docstring); raises ValueError."""
+    for name, alpha in (("mixup", alpha_mix), ("cutmix", alpha_cut)):
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(
+                f"{name} alpha must be in [0, 1] (0 = off), got {alpha}: "
+                "lambda ~ Beta(alpha, alpha) is drawn by Joehnk's method with "
+                "one try per lane of a wave, and its acceptance rate drops "
+                "below 1/2 for alpha > 1")
+    if alpha_mix == 0 and alpha_cut == 0:
+        raise ValueError("mixup and cutmix alpha are both 0: nothing to draw")
+    for name, p in (("prob", prob), ("switch_prob", switch_prob)):
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"mix {name} must be in [0, 1], got {p}")
+
+
+def mix_draw(H, W, alpha_mix, alpha_cut, prob, switch_prob, call_id, step):
+    """The mix params record of one draw under the current key, in float64:
+    the mirror of ``mix::draw_kernel`` (same counters, same word use).
+
+    Returns a dict: ``lam`` (label weight), ``a`` (blend weight), ``y0 y1 x0
+    x1`` (box), ``mode`` (0 not applied, 1 mixup, 2 cutmix), ``raw`` (lambda as
+    drawn, before the box correction), plus ``cy cx`` (box centre) and
+    ``knife``: True where a float32 evaluation may legitimately decide
+    otherwise, i.e. a try up to the winner has ``|X + Y - 1| < 1e-4`` or,
+    under cutmix, ``H sqrt(1 - lambda)`` or ``W sqrt(1 - lambda)`` lies within
+    1e-3 of an integer >= 1.  ``step`` may be an array; every value is then an
+    array over the steps."""
+    check_mix_args(alpha_mix, alpha_cut, prob, switch_prob)
+    scalar = np.ndim(step) == 0
+    steps = np.atleast_1d(np.asarray(step)).astype(np.uint64) & np.uint64(_MASK32)
+    n = steps.shape[0]
+    k0, k1 = key()
+    c0 = np.broadcast_to(np.arange(65, dtype=np.uint64)[None, :], (n, 65))
+    w = philox4x32_10(c0, call_id & _MASK32, (call_id >> 32) & _MASK32,
+                      steps[:, None], k0, k1)
+    w = [np.broadcast_to(a, (n, 65)) for a in w]
+    choice = [a[:, 64] for a in w]
+    applied = choice[0] < np.uint64(keep_threshold(prob))
+    if alpha_mix == 0:
+        cut = np.ones(n, dtype=bool)
+    elif alpha_cut == 0:
+        cut = np.zeros(n, dtype=bool)
+    else:
+        cut = choice[1] < np.uint64(keep_threshold(switch_prob))
+    inv_alpha = 1.0 / np.where(cut, alpha_cut or 1.0, alpha_mix or 1.0)
+    X = ((w[0][:, :64].astype(np.float64) + 0.5) * 2.0 ** -32) ** inv_alpha[:, None]
+    Y = ((w[1][:, :64].astype(np.float64) + 0.5) * 2.0 ** -32) ** inv_alpha[:, None]
+    s = X + Y
+    acc = s <= 1.0
+    hit = acc.any(axis=1)
+    win = np.where(hit, acc.argmax(axis=1), 63)
+    rows = np.arange(n)
+    xs, ys = X[rows, win], Y[rows, win]
+    raw = np.where(hit, xs / (xs + ys), 0.5)
+    oml = np.where(hit, ys / (xs + ys), 0.5)  # 1 - lambda, no cancellation
+    tried = np.arange(64)[None, :] <= win[:, None]
+    knife = ((np.abs(s - 1.0) < 1e-4) & tried).any(axis=1)
+
+    cy = (choice[2] % np.uint64(H)).astype(np.int64)
+    cx = (choice[3] % np.uint64(W)).astype(np.int64)
+    hr, wr = H * np.sqrt(oml), W * np.sqrt(oml)
+    bh, bw = np.floor(hr).astype(np.int64), np.floor(wr).astype(np.int64)
+    y0, y1 = np.clip(cy - bh // 2, 0, H), np.clip(cy + bh // 2, 0, H)
+    x0, x1 = np.clip(cx - bw // 2, 0, W), np.clip(cx + bw // 2, 0, W)
+
+    def near_int(v):
+        return (np.abs(v - np.rint(v)) < 1e-3) & (np.rint(v) >= 1)
+
+    is_cut, is_mix = applied & cut, applied & ~cut
+    knife = applied & (knife | (cut & (near_int(hr) | near_int(wr))))
+    area = (y1 - y0) * (x1 - x0)
+    lam_cut = ((H * W - area).astype(np.float32)
+               / np.float32(H * W)).astype(np.float64)
+    zero = np.zeros(n, dtype=np.int64)
+    out = {
+        "lam": np.where(is_cut, lam_cut, np.where(is_mix, raw, 1.0)),
+        "a": np.where(is_mix, raw, 1.0),
+        "y0": np.where(is_cut, y0, zero), "y1": np.where(is_cut, y1, zero),
+        "x0": np.where(is_cut, x0, zero), "x1": np.where(is_cut, x1, zero),
+        "mode": is_mix * MIX_MIXUP + is_cut * MIX_CUTMIX,
+        "raw": np.where(applied, raw, 1.0),
+        "cy": cy, "cx": cx, "knife": knife,
+    }
+    if scalar:
+        out = {k: v[0].item() for k, v in out.items()}
+    return out
+
+
+def mix_record(lam=1.0, a=1.0, box=(0, 0, 0, 0), mode=MIX_NONE, raw=None):
+    """The 8-slot float32 record (CPU) the mix and loss kernels read: lam, a,
+    then y0 y1 x0 x1 and mode as int32 bit patterns, then raw."""
+    rec = torch.zeros(8, dtype=torch.float32)
+    rec[0], rec[1] = float(lam), float(a)
+    rec[7] = float(lam if raw is None else raw)
+    rec.view(torch.int32)[2:7] = torch.tensor([*box, mode], dtype=torch.int32)
+    return rec
