@@ -1,5 +1,6 @@
 from .foo import FooModel
 from .resnet import ResNet, resnet18, resnet50
+from .convnext import ConvNeXt, convnext_tiny
 from .vit import ViT, vit_b16
 
 
@@ -7,17 +8,27 @@ def is_vit(name: str) -> bool:
     return name.lower() in ("vit-b16", "vit_b16", "vitb16")
 
 
+def is_convnext(name: str) -> bool:
+    return name.lower() in ("convnext-t", "convnext_t", "convnext_tiny")
+
+
 def build_model(name: str, num_classes: int | None = None,
                 dropout: float = 0.0, drop_path: float = 0.0,
                 attn_dropout: float = 0.0):
     """Factory used by the CLI / bench: name -> model instance.
 
-    ``dropout`` / ``drop_path`` / ``attn_dropout`` are the ViT's regularisers;
-    a nonzero rate with any other model is an error."""
+    ``dropout`` / ``drop_path`` / ``attn_dropout`` are the ViT's regularisers
+    and ``drop_path`` is also ConvNeXt's; a nonzero rate with any other model
+    is an error."""
     name = name.lower()
-    if (dropout or drop_path or attn_dropout) and not is_vit(name):
+    if (dropout or attn_dropout) and not is_vit(name):
         raise ValueError(
-            "dropout / drop_path / attn_dropout are only wired into the ViT, "
+            "dropout / attn_dropout are only wired into the ViT, "
+            f"not {name!r}"
+        )
+    if drop_path and not (is_vit(name) or is_convnext(name)):
+        raise ValueError(
+            "drop_path is only wired into the ViT and ConvNeXt, "
             f"not {name!r}"
         )
     if name in ("foo", "foomodel", "mlp"):
@@ -31,6 +42,8 @@ def build_model(name: str, num_classes: int | None = None,
     if is_vit(name):
         return vit_b16(num_classes or 1000, dropout=dropout,
                        drop_path=drop_path, attn_dropout=attn_dropout)
+    if is_convnext(name):
+        return convnext_tiny(num_classes or 1000, drop_path=drop_path)
     raise ValueError(f"unknown model {name!r}")
 
 
@@ -41,5 +54,7 @@ __all__ = [
     "resnet50",
     "ViT",
     "vit_b16",
+    "ConvNeXt",
+    "convnext_tiny",
     "build_model",
 ]

@@ -184,6 +184,14 @@ torch::Tensor attn_dropout(torch::Tensor x, torch::Tensor step, int64_t key0,
                            int64_t key1, int64_t call_id, double p);
 int64_t dropout_grid_cap();
 int64_t dropout_block();
+// dwconv.hip: depthwise conv, x [N,H,W,C], w [C,R,R,1], stride 1
+torch::Tensor dwconv2d_fwd(torch::Tensor x, torch::Tensor w,
+                           c10::optional<torch::Tensor> bias, int64_t pad);
+torch::Tensor dwconv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t pad,
+                             int64_t H, int64_t W);
+torch::Tensor dwconv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t pad,
+                             int64_t R);
+int64_t dwconv_wgrad_block_cap();
 
 // ======================= routing helpers =================================
 
@@ -411,6 +419,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Kout"),
         py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"));
   m.def("conv2d_wgrad", &conv2d_wgrad);
+  m.def("dwconv2d_fwd", &dwconv2d_fwd, py::arg("x"), py::arg("w"),
+        py::arg("bias") = c10::nullopt, py::arg("pad") = 0);
+  m.def("dwconv2d_dgrad", &dwconv2d_dgrad, py::arg("dy"), py::arg("w"),
+        py::arg("pad"), py::arg("H"), py::arg("W"));
+  m.def("dwconv2d_wgrad", &dwconv2d_wgrad, py::arg("dy"), py::arg("x"),
+        py::arg("pad"), py::arg("R"));
+  m.def("dwconv_wgrad_block_cap", &dwconv_wgrad_block_cap);
   m.def("relu_fwd", &relu_fwd);
   m.def("relu_bwd", &relu_bwd);
   m.def("add_relu_fwd", &add_relu_fwd);

@@ -284,8 +284,84 @@ class _Conv2dFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
-def conv2d_nhwc(x, w, b=None, stride=1, pad=0, act=None):
-    return _Conv2dFn.apply(x, w, b, stride, pad, act)
+class _DwConv2dFn(torch.autograd.Function):
+    """Depthwise conv, stride 1: x (N, H, W, C), w (C, R, R, 1).  GPU: the
+    dw:: kernels of ops/csrc/dwconv.hip (the data gradient is the forward
+    kernel with reversed taps, the weight gradient a two-stage fixed-order
+    reduction).  CPU: torch's grouped conv in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, pad):
+        if use_native(x, w):
+            y = native().dwconv2d_fwd(x.contiguous(), w.contiguous(), b, pad)
+        else:
+            C = x.shape[-1]
+            y = F.conv2d(
+                x.permute(0, 3, 1, 2).float(), w.permute(0, 3, 1, 2).float(),
+                b.float() if b is not None else None, 1, pad, groups=C)
+            y = y.permute(0, 2, 3, 1).contiguous().to(x.dtype)
+        ctx.save_for_backward(x, w)
+        ctx.meta = (pad, b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        pad, has_bias = ctx.meta
+        dy = dy.contiguous()
+        C, R = x.shape[-1], w.shape[1]
+        if use_native(dy, w):
+            ext = native()
+            dx = (
+                ext.dwconv2d_dgrad(dy, w.contiguous(), pad, x.shape[1],
+                                   x.shape[2])
+                if ctx.needs_input_grad[0]
+                else None
+            )
+            dw = (
+                ext.dwconv2d_wgrad(dy, x.contiguous(), pad, R).to(w.dtype)
+                if ctx.needs_input_grad[1]
+                else None
+            )
+            db = (
+                ext.col_sum(dy.reshape(-1, C)).to(w.dtype)
+                if has_bias and ctx.needs_input_grad[2]
+                else None
+            )
+        else:
+            dyc = dy.permute(0, 3, 1, 2).float()
+            xc = x.permute(0, 3, 1, 2).float()
+            wc = w.permute(0, 3, 1, 2).float()
+            dxc = torch.nn.grad.conv2d_input(xc.shape, wc, dyc, 1, pad, groups=C)
+            dwc = torch.nn.grad.conv2d_weight(xc, wc.shape, dyc, 1, pad,
+                                              groups=C)
+            dx = dxc.permute(0, 2, 3, 1).contiguous().to(x.dtype)
+            dw = dwc.permute(0, 2, 3, 1).contiguous().to(w.dtype)
+            db = dy.sum(dim=(0, 1, 2)).to(w.dtype) if has_bias else None
+        return dx, dw, db, None
+
+
+def conv2d_nhwc(x, w, b=None, stride=1, pad=0, act=None, groups=1):
+    """groups == 1: the dense implicit-GEMM routes.  groups == C == K with
+    w (C, R, R, 1): depthwise, R in {3, 5, 7}, stride 1, no fused activation
+    (and C % 8 == 0 on the GPU).  Any other grouping is an error."""
+    if groups == 1:
+        return _Conv2dFn.apply(x, w, b, stride, pad, act)
+    C = x.shape[-1]
+    if not (groups == C == w.shape[0] and w.shape[-1] == 1):
+        raise ValueError(
+            f"conv2d_nhwc: groups={groups} with x channels {C} and weight "
+            f"{tuple(w.shape)}: only groups == 1 and depthwise "
+            "(groups == C == K, one input channel per group) are implemented")
+    if stride != 1 or act is not None:
+        raise ValueError("conv2d_nhwc: depthwise needs stride 1 and no act")
+    if w.shape[1] != w.shape[2] or w.shape[1] not in (3, 5, 7):
+        raise ValueError(
+            "conv2d_nhwc: depthwise taps must be square 3, 5 or 7, got "
+            f"{tuple(w.shape[1:3])}")
+    if not 0 <= pad <= w.shape[1] - 1:
+        raise ValueError(f"conv2d_nhwc: depthwise pad {pad} not in [0, R-1]")
+    return _DwConv2dFn.apply(x, w, b, pad)
 
 
 # ---------------------------------------------------------------------------

@@ -81,10 +81,12 @@ class DropPath(nn.Module):
 
 
 class Conv2dNHWC(nn.Module):
-    """Conv2d on (N, H, W, C) tensors; weight stored (K, R, S, C)."""
+    """Conv2d on (N, H, W, C) tensors; weight stored (K, R, S, C / groups).
+    groups: 1, or in_ch == out_ch for a depthwise conv."""
 
     def __init__(
-        self, in_ch, out_ch, kernel_size, stride=1, padding=0, bias=False, act=None
+        self, in_ch, out_ch, kernel_size, stride=1, padding=0, bias=False,
+        act=None, groups=1
     ):
         super().__init__()
         k = (
@@ -92,28 +94,34 @@ class Conv2dNHWC(nn.Module):
             if isinstance(kernel_size, int)
             else tuple(kernel_size)
         )
-        self.in_ch, self.out_ch = in_ch, out_ch
+        if in_ch % groups or out_ch % groups:
+            raise ValueError("Conv2dNHWC: groups must divide in_ch and out_ch")
+        self.in_ch, self.out_ch, self.groups = in_ch, out_ch, groups
         self.kernel_size, self.stride, self.padding = k, stride, padding
         self.act = act
-        self.weight = nn.Parameter(torch.empty(out_ch, k[0], k[1], in_ch))
+        self.weight = nn.Parameter(
+            torch.empty(out_ch, k[0], k[1], in_ch // groups))
         self.bias = nn.Parameter(torch.empty(out_ch)) if bias else None
         self.reset_parameters()
 
     def reset_parameters(self):
-        fan_in = self.in_ch * self.kernel_size[0] * self.kernel_size[1]
+        fan_in = (self.in_ch // self.groups) * self.kernel_size[0] \
+            * self.kernel_size[1]
         nn.init.normal_(self.weight, 0.0, math.sqrt(2.0 / fan_in))
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
     def forward(self, x):
         return X.conv2d_nhwc(
-            x, self.weight, self.bias, self.stride, self.padding, self.act
+            x, self.weight, self.bias, self.stride, self.padding, self.act,
+            self.groups
         )
 
     def extra_repr(self):
         return (
             f"{self.in_ch}, {self.out_ch}, kernel_size={self.kernel_size},"
             f" stride={self.stride}, padding={self.padding}, act={self.act}"
+            + (f", groups={self.groups}" if self.groups != 1 else "")
         )
 
 
