@@ -49,6 +49,7 @@ class BasicBlock(nn.Module):
         # off for a standalone block, ResNet wires consecutive blocks
         self._out_to_block = False
         self._in_from_block = False
+        self._in_from_stem = False
         self.conv1 = _conv_bn(in_ch, ch, 3, stride, 1, act="relu")
         self.conv2 = _conv_bn(ch, ch, 3, 1, 1)
         self.down = (
@@ -79,7 +80,8 @@ class BasicBlock(nn.Module):
                 self.down[0] if self.down is not None else None,
                 self.down[1] if self.down is not None else None,
                 self.stride,
-                offer=self._out_to_block, accept=self._in_from_block,
+                offer=self._out_to_block,
+                accept=self._in_from_block or self._in_from_stem,
             )
         idt = x if self.down is None else self.down(x)
         out = self.conv2(self.conv1(x))
@@ -94,6 +96,7 @@ class Bottleneck(nn.Module):
         self.stride = stride
         self._out_to_block = False
         self._in_from_block = False
+        self._in_from_stem = False
         self.conv1 = _conv_bn(in_ch, ch, 1, 1, 0, act="relu")
         self.conv2 = _conv_bn(ch, ch, 3, stride, 1, act="relu")
         self.conv3 = _conv_bn(ch, ch * self.expansion, 1, 1, 0)
@@ -118,7 +121,8 @@ class Bottleneck(nn.Module):
                 self.down[0] if self.down is not None else None,
                 self.down[1] if self.down is not None else None,
                 self.stride,
-                offer=self._out_to_block, accept=self._in_from_block,
+                offer=self._out_to_block,
+                accept=self._in_from_block or self._in_from_stem,
             )
         idt = x if self.down is None else self.down(x)
         out = self.conv3(self.conv2(self.conv1(x)))
@@ -157,11 +161,18 @@ class ResNet(nn.Module):
         self.pool = GlobalAvgPoolNHWC()
         self.fc = Linear(512 * block.expansion, num_classes)
         # consecutive blocks (across the layer boundaries too) hand over a
-        # pre-masked gradient.  The first block does not mask the stem
-        # output's grad (the stem's bn_bwd applies that ReLU mask itself);
-        # the last block keeps its relu_bwd (the average pool does not mask).
+        # pre-masked gradient; the last block keeps its relu_bwd (the average
+        # pool does not mask).
         wire_blocks([b for layer in (self.layer1, self.layer2, self.layer3,
                                      self.layer4) for b in layer])
+        # A BN+ReLU stem whose output goes straight into layer1 makes the
+        # same offer (its node settles per forward whether the first block
+        # masks the gradient and hands over the BN-backward sums, else its
+        # bn_bwd applies the ReLU mask itself).  Not the ImageNet stem: the
+        # maxpool sits between.
+        if stem == "cifar":
+            self.stem[0][1]._out_to_block = True
+            self.layer1[0]._in_from_stem = True
 
     def _make_layer(self, block, ch, n, stride):
         blocks = [block(self.in_ch, ch, stride)]

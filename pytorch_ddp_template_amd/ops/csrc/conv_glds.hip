@@ -15,7 +15,7 @@
 // col sums/sumsq) matching the NT/halo workspace convention so the fused
 // conv+BN path (bn_fwd_ws) consumes it unchanged.  Optional dgrad epilogue
 // (skip-grad addend and/or ReLU mask in the coalesced store phase, EPI_*).
-// With EPI_BNSTATS the masked dgrad also leaves the per-channel BatchNorm
+// With EPI_BNSTATS the masked dgrad (with or without the addend) also leaves the per-channel BatchNorm
 // backward sums (sum dz, sum dz*xhat) of the BN it feeds in a workspace that
 // bn_bwd_finalize_kernel consumes, so that BN's stats pass disappears
 // (bn_bwd_ws) — the backward mirror of the forward stats epilogue.
@@ -91,11 +91,15 @@ struct Geom {
 // passes it replaces.
 constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_MASK = 2, EPI_ADD_MASK = 3;
 // bit 2 = BN-backward sums of the stored (masked) values; only together with
-// the mask and without an addend.  The addend operand slot then carries the
-// BN input t, and for every stored element v (column c)
+// the mask.  For every stored element v (column c) and BN input t
 //   ws[R + row][c] += v          ws[row][c] += v * (t - mean[c]) * rstd[c]
 // with row = block id % R: the [2R][C] layout of bn_bwd_stats_kernel.
+// Without an addend (EPI_MASK_BNSTATS: the in-block BN+ReLU) the addend
+// operand slot carries t; with one (EPI_ADD_MASK_BNSTATS: a block's last
+// dgrad, whose masked sum is the gradient of the upstream block's last BN) t
+// is a third operand stream, bn_x.
 constexpr int EPI_BNSTATS = 4, EPI_MASK_BNSTATS = EPI_MASK | EPI_BNSTATS;
+constexpr int EPI_ADD_MASK_BNSTATS = EPI_ADD | EPI_MASK | EPI_BNSTATS;
 
 // Halo-resident A operand (HW != 0; 64-wide tile, 3x3 stride-1 pad-1, C = 64,
 // image width HW): a 256-row M-tile is BM/HW whole rows of one image, so its
@@ -154,11 +158,13 @@ void conv_fwd_glds_kernel(
     float* __restrict__ stats_ws, int ws_nblocks,
     const __hip_bfloat16* __restrict__ addend,
     const __hip_bfloat16* __restrict__ out_mask,
-    const float* __restrict__ bn_mean, const float* __restrict__ bn_rstd) {
+    const float* __restrict__ bn_mean, const float* __restrict__ bn_rstd,
+    const __hip_bfloat16* __restrict__ bn_x) {
   static_assert(!(STATS && EPI != EPI_NONE),
                 "dgrad epilogues carry no forward stats");
-  static_assert(!(EPI & EPI_BNSTATS) || EPI == EPI_MASK_BNSTATS,
-                "BN-backward sums ride only with the mask, without an addend");
+  static_assert(!(EPI & EPI_BNSTATS) || EPI == EPI_MASK_BNSTATS ||
+                    EPI == EPI_ADD_MASK_BNSTATS,
+                "BN-backward sums ride only with the mask");
   static_assert(HW == 0 || ((BN == 64 || (BN == 128 && HW == 16)) &&
                             BM % HW == 0 && HW % 16 == 0),
                 "halo variant: 64-wide tile, or 128-wide at HW = 16; whole "
@@ -473,10 +479,12 @@ void conv_fwd_glds_kernel(
   // the store loop (never all NR rounds in registers at once).
   constexpr bool HAS_ADD = (EPI & EPI_ADD) != 0;
   constexpr bool HAS_MASK = (EPI & EPI_MASK) != 0;
-  constexpr bool HAS_BNS = (EPI & EPI_BNSTATS) != 0;  // av[] carries t
+  constexpr bool HAS_BNS = (EPI & EPI_BNSTATS) != 0;
+  // BN input t: its own stream (tv[]) next to an addend, else av[] carries it
+  constexpr bool HAS_T3 = HAS_BNS && HAS_ADD;
   constexpr int PF = 2;
   static_assert(NR >= PF, "epilogue prefetch deeper than the store loop");
-  short8 av[PF] = {}, mv[PF] = {};
+  short8 av[PF] = {}, mv[PF] = {}, tv[PF] = {};
   // y row of a tile row; PAR: dx pixel (n, 2i + pa, 2j + pb) of dy position
   // m0 + row = (n, i, j)
   auto yrow = [&](int row) -> long long {
@@ -496,6 +504,8 @@ void conv_fwd_glds_kernel(
       av[slot] = *(const short8*)((const char*)addend + off);
     if constexpr (HAS_MASK)
       mv[slot] = *(const short8*)((const char*)out_mask + off);
+    if constexpr (HAS_T3)
+      tv[slot] = *(const short8*)((const char*)bn_x + off);
   };
   if constexpr (EPI != EPI_NONE) {
 #pragma unroll
@@ -554,13 +564,16 @@ void conv_fwd_glds_kernel(
     auto store_round = [&](int r, int slot) {
       const int row = r * RPR + wrow;
       short8 c = *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
-      const short8 t = av[slot], m = mv[slot];
+      const short8 a = av[slot], m = mv[slot];
+      const short8 t = HAS_T3 ? tv[slot] : a;
       if (r + PF < NR) epi_load(r + PF, slot);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        // the stored value, exactly as EPI_MASK stores it; the sums use the
-        // expression of bn_bwd_stats_kernel
-        const float gv = bfbits2f(m[j]) > 0.f ? bfbits2f(c[j]) : 0.f;
+        // the stored value, exactly as EPI_MASK / EPI_ADD_MASK store it; the
+        // sums use the expression of bn_bwd_stats_kernel
+        short v = c[j];
+        if constexpr (HAS_ADD) v = f2bfbits(bfbits2f(v) + bfbits2f(a[j]));
+        const float gv = bfbits2f(m[j]) > 0.f ? bfbits2f(v) : 0.f;
         c[j] = f2bfbits(gv);
         sdb[j] += gv;
         sdg[j] += gv * (bfbits2f(t[j]) - mu[j]) * rs[j];
@@ -682,8 +695,9 @@ bool conv_dgrad_s2_parity_eligible(int64_t H, int64_t W, int64_t Cin,
 // [N,HO,WO,Kout]; stats_ws (optional) pre-zeroed [2*ws_nblocks, Kout].
 // addend / out_mask (optional, dgrad only, never with stats_ws): y-shaped
 // contiguous tensors applied in the store phase — see cg::EPI_*.
-// bns (optional, with out_mask only): also emit the BN-backward sums; the
-// zeroed workspace is allocated here, once the shape is known to be taken.
+// bns (optional, with out_mask only, with or without addend): also emit the
+// BN-backward sums; the zeroed workspace is allocated here, once the shape is
+// known to be taken.
 static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
                                torch::Tensor& y, const torch::Tensor& zp,
                                int64_t stride, int64_t pad, float* stats_ws,
@@ -724,9 +738,10 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
   const bf16* addp = addend.has_value() ? ptr16<bf16>(*addend) : nullptr;
   const bf16* maskp = out_mask.has_value() ? ptr16<bf16>(*out_mask) : nullptr;
   const float *meanp = nullptr, *rstdp = nullptr;
+  const bf16* bnxp = nullptr;
   if (bns) {
-    TORCH_CHECK(epi == cg::EPI_MASK && !stats_ws,
-                "conv glds: BN-backward sums need out_mask and no addend");
+    TORCH_CHECK((epi & cg::EPI_MASK) && !stats_ws,
+                "conv glds: BN-backward sums need out_mask");
     TORCH_CHECK(bns->bn_x.is_cuda() && bns->bn_x.is_contiguous() &&
                     bns->bn_x.scalar_type() == x.scalar_type() &&
                     bns->bn_x.numel() == y.numel(),
@@ -742,7 +757,9 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
     bns->ws = torch::zeros({2LL * ws_nblocks, Kout},
                            x.options().dtype(torch::kFloat32));
     stats_ws = bns->ws.data_ptr<float>();
-    addp = ptr16<bf16>(bns->bn_x);  // rides in the addend operand slot
+    // without an addend t rides in the addend operand slot
+    if (addp) bnxp = ptr16<bf16>(bns->bn_x);
+    else addp = ptr16<bf16>(bns->bn_x);
     meanp = bns->mean.data_ptr<float>();
     rstdp = bns->rstd.data_ptr<float>();
   }
@@ -779,7 +796,9 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
    : BN == 256 ? &cg::conv_fwd_glds_kernel<256, false, EP, 0, true>       \
    : BN == 128 ? &cg::conv_fwd_glds_kernel<128, false, EP, 0, true>       \
                : &cg::conv_fwd_glds_kernel<64, false, EP, 0, true>)
-  auto kern = bns                     ? CG_DGRAD(cg::EPI_MASK_BNSTATS)
+  auto kern = bns && addend.has_value()
+                  ? CG_DGRAD(cg::EPI_ADD_MASK_BNSTATS)
+              : bns                   ? CG_DGRAD(cg::EPI_MASK_BNSTATS)
               : stats_ws              ? CG_KERN(true, cg::EPI_NONE)
               : epi == cg::EPI_NONE   ? CG_DGRAD(cg::EPI_NONE)
               : epi == cg::EPI_ADD    ? CG_DGRAD(cg::EPI_ADD)
@@ -791,7 +810,7 @@ static bool conv2d_glds_launch(const torch::Tensor& x, const torch::Tensor& w,
   hipLaunchKernelGGL(kern, grid, dim3(cg::THREADS), 0, stream, ptr16<bf16>(x),
                      ptr16<bf16>(w), ptr16<bf16>(y), ptr16<bf16>(zp), (int)M,
                      Kout, K, g, stats_ws, ws_nblocks, addp, maskp, meanp,
-                     rstdp);
+                     rstdp, bnxp);
   return true;
 }
 
@@ -805,17 +824,19 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
                             lgSt, addend, out_mask, nullptr);
 }
 
-// Masked dgrad that also emits the BN-backward sums of the BN it feeds.
+// Masked dgrad (plus the optional addend, added before the mask) that also
+// emits the BN-backward sums of the BN it feeds.
 // Returns the workspace ([2R][C]: rows [0,R) sum dz*xhat, [R,2R) sum dz), or
 // an undefined tensor when the kernel declines the shape (nothing launched).
 torch::Tensor conv2d_dgrad_glds_bnstats(
     const torch::Tensor& dy, const torch::Tensor& wr, torch::Tensor& dx,
     const torch::Tensor& zp, int64_t pad, int lgSt,
-    const torch::Tensor& out_mask, const torch::Tensor& bn_x,
-    const torch::Tensor& bn_mean, const torch::Tensor& bn_rstd) {
+    const c10::optional<torch::Tensor>& addend, const torch::Tensor& out_mask,
+    const torch::Tensor& bn_x, const torch::Tensor& bn_mean,
+    const torch::Tensor& bn_rstd) {
   GldsBnStats bns{bn_x, bn_mean, bn_rstd, torch::Tensor()};
-  if (!conv2d_glds_launch(dy, wr, dx, zp, 1, pad, nullptr, 0, lgSt,
-                          c10::nullopt, out_mask, &bns))
+  if (!conv2d_glds_launch(dy, wr, dx, zp, 1, pad, nullptr, 0, lgSt, addend,
+                          out_mask, &bns))
     return torch::Tensor();
   return bns.ws;
 }

@@ -992,8 +992,9 @@ bool conv2d_fwd_glds_ex(const torch::Tensor& x, const torch::Tensor& w,
 torch::Tensor conv2d_dgrad_glds_bnstats(
     const torch::Tensor& dy, const torch::Tensor& wr, torch::Tensor& dx,
     const torch::Tensor& zp, int64_t pad, int lgSt,
-    const torch::Tensor& out_mask, const torch::Tensor& bn_x,
-    const torch::Tensor& bn_mean, const torch::Tensor& bn_rstd);
+    const c10::optional<torch::Tensor>& addend, const torch::Tensor& out_mask,
+    const torch::Tensor& bn_x, const torch::Tensor& bn_mean,
+    const torch::Tensor& bn_rstd);
 // elementwise.hip
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y);
 
@@ -1075,8 +1076,8 @@ std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
 // kernel's coalesced store phase (bit-identical to separate add_ / relu_bwd
 // passes); elsewhere the addend uses the NT kernel's EXTRAS epilogue and
 // out_mask a relu_bwd pass over the result.
-// bns (optional; needs out_mask, excludes addend): ask the glds route for the
-// BN-backward sums of the masked dx as well; bns->ws stays undefined when
+// bns (optional; needs out_mask, excludes addend_mask): ask the glds route for
+// the BN-backward sums of the masked dx as well; bns->ws stays undefined when
 // another route ran, which returns the same masked dx and no sums.
 struct DgradBnStats {
   torch::Tensor bn_x, mean, rstd;
@@ -1131,7 +1132,7 @@ static torch::Tensor conv2d_dgrad_bf16_impl(
       ((int)stride == 1 || glds_s2)) {
     const int lgSt = log2_exact((int)stride);
     if (lgSt >= 0 && bns) {
-      bns->ws = conv2d_dgrad_glds_bnstats(dy, wr, dx, zp, dpad, lgSt,
+      bns->ws = conv2d_dgrad_glds_bnstats(dy, wr, dx, zp, dpad, lgSt, addend,
                                           *out_mask, bns->bn_x, bns->mean,
                                           bns->rstd);
       if (bns->ws.defined()) return dx;
@@ -1172,15 +1173,18 @@ torch::Tensor conv2d_dgrad_bf16(torch::Tensor dy, torch::Tensor wr,
                                 out_mask, nullptr);
 }
 
-// dx = relu_bwd(dgrad, out_mask) plus, when the glds kernel took the call,
-// the BN-backward sums workspace of the BN whose ReLU output is out_mask and
-// whose input is bn_x (conv_glds.hip, EPI_BNSTATS).  Returns {dx} or {dx, ws}.
+// dx = relu_bwd(dgrad + addend, out_mask), the addend optional, plus, when the
+// glds kernel took the call, the BN-backward sums workspace of the BN whose
+// input is bn_x and whose gradient dx is (conv_glds.hip, EPI_BNSTATS): without
+// an addend the BN whose ReLU output is out_mask, with one the last BN of the
+// upstream block.  Returns {dx} or {dx, ws}.
 std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
     torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
     int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
-    torch::Tensor bn_mean, torch::Tensor bn_rstd) {
+    torch::Tensor bn_mean, torch::Tensor bn_rstd,
+    c10::optional<torch::Tensor> addend) {
   DgradBnStats bns{bn_x, bn_mean, bn_rstd, torch::Tensor()};
-  auto dx = conv2d_dgrad_bf16_impl(dy, wr, stride, pad, H, W, c10::nullopt,
+  auto dx = conv2d_dgrad_bf16_impl(dy, wr, stride, pad, H, W, addend,
                                    c10::nullopt, out_mask, &bns);
   if (bns.ws.defined()) return {dx, bns.ws};
   return {dx};

@@ -57,7 +57,8 @@ std::vector<torch::Tensor> conv2d_fwd_stats_bf16(
 std::vector<torch::Tensor> conv2d_dgrad_bnstats_bf16(
     torch::Tensor dy, torch::Tensor wr, int64_t stride, int64_t pad, int64_t H,
     int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
-    torch::Tensor bn_mean, torch::Tensor bn_rstd);
+    torch::Tensor bn_mean, torch::Tensor bn_rstd,
+    c10::optional<torch::Tensor> addend);
 // conv_glds.hip: does a conv shape take the halo-resident 64-wide tile
 bool conv_halo64_eligible(int64_t H, int64_t W, int64_t C, int64_t Kout,
                           int64_t R, int64_t S, int64_t stride, int64_t pad);
@@ -329,24 +330,28 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
   return dx;
 }
 
-// conv2d_dgrad(..., out_mask=out_mask) that, when the glds kernel takes the
-// call, also returns the BN-backward sums workspace of the BN with input
-// bn_x, saved bn_mean / bn_rstd and ReLU output out_mask (for bn_bwd_ws).
-// Every other route returns the same masked dx and None.
+// conv2d_dgrad(..., addend=addend, out_mask=out_mask) that, when the glds
+// kernel takes the call, also returns the BN-backward sums workspace (for
+// bn_bwd_ws) of the BN with input bn_x and saved bn_mean / bn_rstd whose
+// output gradient dx is: without an addend the BN whose ReLU output is
+// out_mask, with one the last BN of the block upstream, whose output is
+// out_mask.  Every other route returns the same masked dx and None.
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv2d_dgrad_bnstats(
     torch::Tensor dy, torch::Tensor w, int64_t stride, int64_t pad, int64_t H,
     int64_t W, torch::Tensor out_mask, torch::Tensor bn_x,
-    torch::Tensor bn_mean, torch::Tensor bn_rstd) {
+    torch::Tensor bn_mean, torch::Tensor bn_rstd,
+    c10::optional<torch::Tensor> addend) {
   int R = (int)w.size(1), S = (int)w.size(2);
   TORCH_CHECK(pad <= R - 1 && pad <= S - 1, "dgrad needs pad <= kernel-1");
   if (is_bf16(dy) && pow2_ge((int)dy.size(3), 8)) {
     auto wr = weight_rot(w.contiguous());  // [C, R, S, Kout]
     auto r = conv2d_dgrad_bnstats_bf16(dy.contiguous(), wr, stride, pad, H, W,
-                                       out_mask, bn_x, bn_mean, bn_rstd);
+                                       out_mask, bn_x, bn_mean, bn_rstd,
+                                       addend);
     if (r.size() == 2) return {r[0], r[1]};
     return {r[0], c10::nullopt};
   }
-  return {conv2d_dgrad(dy, w, stride, pad, H, W, c10::nullopt, c10::nullopt,
+  return {conv2d_dgrad(dy, w, stride, pad, H, W, addend, c10::nullopt,
                        out_mask),
           c10::nullopt};
 }
@@ -401,7 +406,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_dgrad_bnstats", &conv2d_dgrad_bnstats, py::arg("dy"),
         py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("out_mask"), py::arg("bn_x"),
-        py::arg("bn_mean"), py::arg("bn_rstd"));
+        py::arg("bn_mean"), py::arg("bn_rstd"),
+        py::arg("addend") = c10::nullopt);
   m.def("conv2d_fwd_stats", &conv2d_fwd_stats_bf16, py::arg("x"),
         py::arg("w"), py::arg("bias") = c10::nullopt, py::arg("stride") = 1,
         py::arg("pad") = 0, py::arg("relu") = false);

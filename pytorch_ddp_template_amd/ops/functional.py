@@ -35,7 +35,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import rng
+from . import fused_block, rng
 from .native import native, use_native
 
 # ---------------------------------------------------------------------------
@@ -370,12 +370,25 @@ def conv2d_nhwc(x, w, b=None, stride=1, pad=0, act=None, groups=1):
 
 
 class _BatchNorm2dFn(torch.autograd.Function):
+    """``offer``: this BN+ReLU feeds a wired fused block and nothing else (the
+    CIFAR ResNet stem).  On the native training path its node then makes the
+    offer a fused block's node makes (ops/fused_block.py): the consumer may
+    mask the gradient it returns by this ReLU and leave the BN-backward sums
+    on the node, and the backward runs ``bn_bwd_ws`` on that gradient."""
+
     @staticmethod
     def forward(
-        ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, act
+        ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps,
+        act, offer=False,
     ):
         C = x.shape[-1]
         xs = x.reshape(-1, C)
+        ctx.dy_premasked = None
+        if (offer and training and act == "relu" and use_native(x, gamma)
+                and x.is_contiguous()
+                and fused_block._use_dgrad_epilogue()
+                and fused_block._use_dgrad_handoff_bnstats()):
+            ctx.dy_premasked = False
         if use_native(x, gamma):
             ext = native()
             if training:
@@ -418,6 +431,8 @@ class _BatchNorm2dFn(torch.autograd.Function):
             if act == "relu":
                 y = torch.relu(y)
             y = y.to(x.dtype)
+        if ctx.dy_premasked is not None:
+            fused_block._offer_bn_sums(ctx, x, mean, rstd)
         ctx.save_for_backward(
             x, gamma, mean, rstd, y if act == "relu" else None
         )
@@ -438,9 +453,17 @@ class _BatchNorm2dFn(torch.autograd.Function):
             # fused relu mask: bn_bwd applies (y_relu > 0) inline — no
             # separate relu_bwd pass over the tensor
             yr = y_relu.reshape(-1, C) if act == "relu" else None
-            dx, dgamma, dbeta = ext.bn_bwd(
-                dys, xs.contiguous(), gamma, mean, rstd, yr
-            )
+            ws = fused_block._take_bn_ws(ctx)
+            if ws is not None:
+                # dy carries the ReLU mask, ws its sums (handed over)
+                dx, dgamma, dbeta = ext.bn_bwd_ws(
+                    dys, xs.contiguous(), gamma, mean, rstd, ws
+                )
+            else:
+                dx, dgamma, dbeta = ext.bn_bwd(
+                    dys, xs.contiguous(), gamma, mean, rstd,
+                    None if ctx.dy_premasked else yr
+                )
             dgamma = dgamma.to(gamma.dtype)
             dbeta = dbeta.to(gamma.dtype)
         else:
@@ -468,6 +491,7 @@ class _BatchNorm2dFn(torch.autograd.Function):
             None,
             None,
             None,
+            None,
         )
 
 
@@ -481,9 +505,11 @@ def batch_norm2d_nhwc(
     momentum=0.1,
     eps=1e-5,
     act=None,
+    offer=False,
 ):
     return _BatchNorm2dFn.apply(
-        x, gamma, beta, running_mean, running_var, training, momentum, eps, act
+        x, gamma, beta, running_mean, running_var, training, momentum, eps, act,
+        offer,
     )
 
 

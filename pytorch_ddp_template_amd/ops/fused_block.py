@@ -42,6 +42,19 @@ so its producer masks as before; a standalone block neither offers nor
 accepts.  The wiring assumes the producer's output has no other consumer
 (true for the ``nn.Sequential`` layers of ``models/resnet.py``).
 
+BN-sums hand-off on top of that handshake (``PDT_DGRAD_HANDOFF_BNSTATS``,
+below): the gradient the consumer hands over pre-masked is exactly the ``dy``
+of the producer's last BatchNorm (``bn2`` of a BasicBlock, ``bn3`` of a
+Bottleneck, or the BN of a BN+ReLU stem), and the consumer's last dgrad holds
+every element of it just before the store.  A producer that offers the
+pre-mask therefore also exposes that BN's ``(t, mean, rstd)`` on its node
+(``bn_offer``); a consumer that accepted the mask runs its last dgrad as
+``conv2d_dgrad_bnstats(..., addend=·)`` with them and leaves the returned
+workspace on the producer's node (``bn_ws``); the producer's backward then
+runs ``bn_bwd_ws`` instead of ``bn_bwd``'s stats pass.  Where the glds kernel
+declines the shape ``bn_ws`` stays ``None`` and nothing changes.  A downsample
+block's ``bnd`` keeps its own stats pass.
+
 The unfused module path (ops/modules.py) remains the CPU/eval/odd-shape
 reference; tests compare the two.  Reference scope note: the reference
 template has no conv/BN at all (these ops come from the
@@ -88,6 +101,14 @@ def _use_dgrad_bnstats():
     return os.environ.get("PDT_DGRAD_BNSTATS", "1") != "0"
 
 
+def _use_dgrad_handoff_bnstats():
+    # BN-backward sums of the upstream block's last BN from this block's last
+    # dgrad (module docstring); PDT_DGRAD_HANDOFF_BNSTATS=0 restores the
+    # separate stats passes, and the unmasked gradient of a BN+ReLU stem (A/B
+    # runs).  Read once per block forward; the backward follows it.
+    return os.environ.get("PDT_DGRAD_HANDOFF_BNSTATS", "1") != "0"
+
+
 def _dgrad_for_bn_relu(ext, bns, dy, w, stride, pad, H, W, t, z, mean, rstd):
     """dgrad of ``dy`` through the conv with weight ``w`` whose input was the
     output ``z`` of a BN+ReLU with BN input ``t``.  Returns (dz, ws, masked):
@@ -123,9 +144,46 @@ def _accept_premask(x, accept, epi):
     return True
 
 
+def _offer_bn_sums(ctx, t, mean, rstd):
+    """Producer side of the BN-sums hand-off: next to an offered pre-mask,
+    expose the BN whose backward consumes the handed-over gradient, and a
+    slot for the sums workspace the consumer may return."""
+    if ctx.dy_premasked is None or not _use_dgrad_handoff_bnstats():
+        return
+    ctx.bn_offer = (t, mean, rstd)
+    ctx.bn_ws = None
+
+
+def _accept_bn_sums(x, mask_in):
+    """Consumer side: x's producer node when this block masks its dx
+    (``mask_in``) and that node offers its BN, else None."""
+    if not (mask_in and _use_dgrad_handoff_bnstats()):
+        return None
+    fn = x.grad_fn
+    return fn if getattr(fn, "bn_offer", None) is not None else None
+
+
+def _take_bn_ws(ctx):
+    """Producer backward: the sums the consumer left, or None; the node keeps
+    neither them nor the offered tensors beyond this backward."""
+    ws = getattr(ctx, "bn_ws", None)
+    if hasattr(ctx, "bn_offer"):
+        ctx.bn_offer = ctx.bn_ws = None
+    return ws
+
+
 def _skip_grad_dgrad(ext, ctx, dyc, w, stride, pad, H, W, addend, x):
     """dx = dgrad(dyc, w) + addend, masked by x > 0 when this block agreed to
-    (ctx.mask_in); fused into the dgrad epilogue unless gated off."""
+    (ctx.mask_in); fused into the dgrad epilogue unless gated off.  With the
+    BN-sums hand-off agreed (ctx.bn_up) the sums of the upstream BN go to its
+    node."""
+    up = ctx.bn_up
+    offer = getattr(up, "bn_offer", None)
+    if offer is not None:
+        t, mean, rstd = offer
+        dx, up.bn_ws = ext.conv2d_dgrad_bnstats(
+            dyc, w, stride, pad, H, W, x, t, mean, rstd, addend=addend)
+        return dx
     if ctx.epi:
         return ext.conv2d_dgrad(dyc, w, stride, pad, H, W, addend=addend,
                                 out_mask=x if ctx.mask_in else None)
@@ -141,12 +199,13 @@ class _FusedBasicBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(
         ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, bn1, bn2, bnd, stride,
-        offer=False, mask_in=False, epi=False, bns=False,
+        offer=False, mask_in=False, epi=False, bns=False, bn_up=None,
     ):
         ext = native()
         # handshake state (module docstring): None = no offer made
         ctx.epi, ctx.mask_in, ctx.bns = epi, mask_in, bns
         ctx.dy_premasked = False if (offer and epi) else None
+        ctx.bn_up = bn_up
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
         t1, ws1 = ext.conv2d_fwd_stats(x, w1, None, stride, 1, False)
@@ -173,6 +232,7 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             mom, eps, True, _flat(idn.contiguous()),
         )
         out = out2.reshape(t2.shape)
+        _offer_bn_sums(ctx, t2, mean2, rstd2)
         ctx.save_for_backward(
             x, w1, g1, t1, z, mean1, rstd1, w2, g2, t2, mean2, rstd2,
             wd, gd, td, meand, rstdd, out,
@@ -195,7 +255,12 @@ class _FusedBasicBlockFn(torch.autograd.Function):
         # downstream block already masked dy in its dgrad epilogue, dy is g.
         g = dy if ctx.dy_premasked else ext.relu_bwd(dy, out)
         g2d = _flat(g)
-        dx2, dg2, db2 = ext.bn_bwd(g2d, _flat(t2), g2, mean2, rstd2, None)
+        ws2 = _take_bn_ws(ctx)
+        if ws2 is not None:
+            dx2, dg2, db2 = ext.bn_bwd_ws(g2d, _flat(t2), g2, mean2, rstd2,
+                                          ws2)
+        else:
+            dx2, dg2, db2 = ext.bn_bwd(g2d, _flat(t2), g2, mean2, rstd2, None)
         dx2 = dx2.reshape(t2.shape)
         use_side = _use_streams()
         main = torch.cuda.current_stream()
@@ -240,7 +305,7 @@ class _FusedBasicBlockFn(torch.autograd.Function):
             for t in (dw2, dw1) + ((dwd,) if wd is not None else ()):
                 t.record_stream(main)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd,
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride,
@@ -259,6 +324,7 @@ def fused_basic_block(x, conv1, bn1, conv2, bn2, convd, bnd, stride,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
         bn1, bn2, bnd, stride, offer, mask_in, epi, bns,
+        _accept_bn_sums(x, mask_in),
     )
 
 
@@ -269,10 +335,11 @@ class _FusedBottleneckFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd,
                 bn1, bn2, bn3, bnd, stride,
-                offer=False, mask_in=False, epi=False, bns=False):
+                offer=False, mask_in=False, epi=False, bns=False, bn_up=None):
         ext = native()
         ctx.epi, ctx.mask_in, ctx.bns = epi, mask_in, bns
         ctx.dy_premasked = False if (offer and epi) else None
+        ctx.bn_up = bn_up
         x = x.contiguous()
         mom, eps = bn1.momentum, bn1.eps
         t1, ws1 = ext.conv2d_fwd_stats(x, w1, None, 1, 0, False)
@@ -300,6 +367,7 @@ class _FusedBottleneckFn(torch.autograd.Function):
             _flat(t3), g3, b3, ws3, bn3.running_mean, bn3.running_var,
             mom, eps, True, _flat(idn.contiguous()))
         out = out3.reshape(t3.shape)
+        _offer_bn_sums(ctx, t3, mean3, rstd3)
         ctx.save_for_backward(
             x, w1, g1, t1, z1, mean1, rstd1, w2, g2, t2, z2, mean2, rstd2,
             w3, g3, t3, mean3, rstd3, wd, gd, td, meand, rstdd, out)
@@ -320,7 +388,12 @@ class _FusedBottleneckFn(torch.autograd.Function):
 
         g = dy if ctx.dy_premasked else ext.relu_bwd(dy, out)
         g2d = _flat(g)
-        dx3, dg3, db3 = ext.bn_bwd(g2d, _flat(t3), g3, mean3, rstd3, None)
+        ws3 = _take_bn_ws(ctx)
+        if ws3 is not None:
+            dx3, dg3, db3 = ext.bn_bwd_ws(g2d, _flat(t3), g3, mean3, rstd3,
+                                          ws3)
+        else:
+            dx3, dg3, db3 = ext.bn_bwd(g2d, _flat(t3), g3, mean3, rstd3, None)
         dx3 = dx3.reshape(t3.shape)
         dz2, ws2, masked = _dgrad_for_bn_relu(
             ext, ctx.bns, dx3, w3, 1, 0, H2, W2, t2, z2, mean2, rstd2)
@@ -347,7 +420,7 @@ class _FusedBottleneckFn(torch.autograd.Function):
             dx = _skip_grad_dgrad(ext, ctx, dtd, wd, stride, 0, H, W, dxa, x)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3,
                 dwd, dgd, dbd, None, None, None, None, None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
@@ -363,4 +436,5 @@ def fused_bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, convd, bnd,
         bnd.weight if bnd is not None else None,
         bnd.bias if bnd is not None else None,
         bn1, bn2, bn3, bnd, stride, offer, mask_in, epi, bns,
+        _accept_bn_sums(x, mask_in),
     )

@@ -140,6 +140,9 @@ class BatchNorm2dNHWC(nn.Module):
         # launch per BN layer per step); it enters state_dict via the
         # _save/_load hooks below so checkpoints still carry it.
         self._batches_tracked = 0
+        # this BN+ReLU's output feeds a wired fused block and nothing else
+        # (functional._BatchNorm2dFn); off unless ResNet wires the stem
+        self._out_to_block = False
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         super()._save_to_state_dict(destination, prefix, keep_vars)
@@ -175,6 +178,7 @@ class BatchNorm2dNHWC(nn.Module):
             self.momentum,
             self.eps,
             self.act,
+            self._out_to_block,
         )
 
     def extra_repr(self):
