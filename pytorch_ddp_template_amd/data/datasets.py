@@ -86,6 +86,7 @@ def build_dataset(name: str, size: int = 100000, dtype: torch.dtype = torch.floa
     if name in ("cifar", "cifar10", "resnet18", "resnet18-cifar"):
         return SyntheticImageDataset(size, 32, 10, dtype=dtype)
     if name in ("imagenet", "resnet18-imagenet", "resnet50", "vit-b16", "vit_b16",
-                "convnext-t", "convnext_t", "convnext_tiny"):
+                "convnext-t", "convnext_t", "convnext_tiny",
+                "swin-t", "swin_t", "swin_tiny"):
         return SyntheticImageDataset(size, 224, 1000, dtype=dtype)
     raise ValueError(f"unknown dataset {name!r}")

@@ -42,6 +42,7 @@ from torch.utils.data import DataLoader
 from .data import CudaPrefetcher, ShardedSampler, build_dataset
 from .models import build_model
 from .models import is_convnext as _is_convnext
+from .models import is_swin as _is_swin
 from .models import is_vit as _is_vit
 from .optim import (
     SGD,
@@ -852,7 +853,7 @@ def build_parser():
     # ---- additive flags (model zoo / MI355X path) ----
     parser.add_argument("--model", type=str, default="foo",
                         help="foo | resnet18 | resnet18-imagenet | resnet50 | vit-b16 "
-                             "| convnext-t")
+                             "| convnext-t | swin-t")
     parser.add_argument("--dataset", type=str, default=None)
     parser.add_argument("--dataset_size", type=int, default=100000)
     parser.add_argument("--learning_rate", "--lr", type=float, default=1e-3)
@@ -869,7 +870,7 @@ def build_parser():
                         help="ViT dropout rate (after the position embedding, "
                              "on the attention projection and both MLP layers)")
     parser.add_argument("--drop_path", type=float, default=0.0,
-                        help="ViT / ConvNeXt stochastic depth: rate of the "
+                        help="ViT / ConvNeXt / Swin stochastic depth: rate of the "
                              "last block, "
                              "growing linearly from 0 at the first")
     parser.add_argument("--attn_dropout", type=float, default=0.0,
@@ -922,7 +923,8 @@ def main(argv=None):
         rate = getattr(args, flag)
         if not 0.0 <= rate < 1.0:
             parser.error(f"--{flag} must be in [0, 1), got {rate}")
-        if flag == "drop_path" and _is_convnext(args.model):
+        if flag == "drop_path" and (_is_convnext(args.model)
+                                    or _is_swin(args.model)):
             continue
         if rate and not _is_vit(args.model):
             parser.error(f"--{flag} is only wired into vit-b16, "

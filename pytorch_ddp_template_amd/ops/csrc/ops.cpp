@@ -193,6 +193,14 @@ torch::Tensor dwconv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t pad,
 torch::Tensor dwconv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t pad,
                              int64_t R);
 int64_t dwconv_wgrad_block_cap();
+// window_attention.hip: 7x7 shifted-window attention, head dim 32;
+// qkv [N,H,W,3*heads*32], bias_table [169,heads], out [N,H,W,heads*32]
+torch::Tensor win_attn_fwd(torch::Tensor qkv, torch::Tensor bias_table,
+                           int64_t heads, int64_t shift, double scale);
+std::vector<torch::Tensor> win_attn_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                        torch::Tensor bias_table,
+                                        int64_t heads, int64_t shift,
+                                        double scale);
 
 // ======================= routing helpers =================================
 
@@ -432,6 +440,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv2d_wgrad", &dwconv2d_wgrad, py::arg("dy"), py::arg("x"),
         py::arg("pad"), py::arg("R"));
   m.def("dwconv_wgrad_block_cap", &dwconv_wgrad_block_cap);
+  m.def("win_attn_fwd", &win_attn_fwd, py::arg("qkv"), py::arg("bias_table"),
+        py::arg("heads"), py::arg("shift"), py::arg("scale"));
+  m.def("win_attn_bwd", &win_attn_bwd, py::arg("dout"), py::arg("qkv"),
+        py::arg("bias_table"), py::arg("heads"), py::arg("shift"),
+        py::arg("scale"));
   m.def("relu_fwd", &relu_fwd);
   m.def("relu_bwd", &relu_bwd);
   m.def("add_relu_fwd", &add_relu_fwd);

@@ -1052,6 +1052,113 @@ def attention(q, k, v, scale, p=0.0, training=True):
 
 
 # ---------------------------------------------------------------------------
+# Shifted-window attention (Swin): 7x7 windows, relative-position bias, mask
+# ---------------------------------------------------------------------------
+
+WINDOW = 7
+_WIN_HEAD_DIM = 32  # what the fused kernels are built for
+
+
+class _WindowAttentionFn(torch.autograd.Function):
+    """Fused window attention from the PACKED qkv map [N, H, W, 3*heads*32]
+    (ops/csrc/window_attention.hip).  Shift, window partition, head split and
+    their inverses are address arithmetic inside the two kernels; scores,
+    probabilities and the mask never exist in memory, and the backward
+    recomputes the probabilities, so only the inputs are saved."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias_table, heads, shift, scale):
+        qkv = qkv.contiguous()
+        ctx.save_for_backward(qkv, bias_table)
+        ctx.args = (heads, shift, scale)
+        return native().win_attn_fwd(qkv, bias_table, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, bias_table = ctx.saved_tensors
+        dqkv, dbias = native().win_attn_bwd(
+            dout.contiguous(), qkv, bias_table, *ctx.args
+        )
+        return dqkv, dbias.to(bias_table.dtype), None, None, None
+
+
+def _window_bias_mask(bias_table, H, W, heads, shift):
+    """The additive term of the scores, [nW or 1, heads, 49, 49]: the table's
+    row (dy+6)*13 + (dx+6) for query - key offset (dy, dx), and -100 between
+    tokens of different regions of the shifted frame."""
+    dev = bias_table.device
+    t = torch.arange(WINDOW * WINDOW, device=dev)
+    ti, tj = t // WINDOW, t % WINDOW
+    rel = (ti[:, None] - ti[None, :] + 6) * 13 + (tj[:, None] - tj[None, :] + 6)
+    add = bias_table[rel.reshape(-1)].reshape(49, 49, heads).permute(2, 0, 1)
+    add = add.unsqueeze(0)
+    if shift == 0:
+        return add
+
+    def region(size, tok):
+        # 0, 1 or 2 for the shifted-frame coordinate 7*w + tok of every
+        # (window, token) along one axis
+        c = torch.arange(size // WINDOW, device=dev)[:, None] * WINDOW + tok
+        return (c >= size - WINDOW).long() + (c >= size - shift).long()
+
+    reg = 3 * region(H, ti)[:, None, :] + region(W, tj)[None, :, :]
+    reg = reg.reshape(-1, 49)                            # [nh*nw, 49]
+    mask = (reg[:, :, None] != reg[:, None, :]).to(add.dtype) * -100.0
+    return add + mask[:, None]
+
+
+def _window_attention_composed(qkv, bias_table, heads, shift, scale):
+    """The same function from torch.roll / reshape copies and the batched
+    GEMM + softmax ops, with scores and probabilities materialised."""
+    N, H, W, C3 = qkv.shape
+    dh = C3 // (3 * heads)
+    nh, nw = H // WINDOW, W // WINDOW
+    x = torch.roll(qkv, (-shift, -shift), (1, 2)) if shift else qkv
+    x = x.reshape(N, nh, WINDOW, nw, WINDOW, 3, heads, dh)
+    x = x.permute(5, 0, 1, 3, 6, 2, 4, 7).reshape(3, -1, 49, dh)
+    q, k, v = x[0].contiguous(), x[1].contiguous(), x[2].contiguous()
+    add = _window_bias_mask(bias_table.to(qkv.dtype), H, W, heads, shift)
+    s = bmm_nt(q, k).reshape(N, nh * nw, heads, 49, 49) * scale + add
+    o = bmm_nn(softmax(s.reshape(-1, 49, 49)), v)
+    o = o.reshape(N, nh, nw, heads, WINDOW, WINDOW, dh)
+    o = o.permute(0, 1, 4, 2, 5, 3, 6).reshape(N, H, W, heads * dh)
+    return torch.roll(o, (shift, shift), (1, 2)) if shift else o
+
+
+def window_attention(qkv, bias_table, heads, shift, scale):
+    """Swin's (shifted-)window multi-head attention on an NHWC map.
+
+    qkv: [N, H, W, 3*heads*32] packed ``[3][heads][32]`` (the qkv Linear's
+    output); bias_table: [169, heads]; returns [N, H, W, heads*32] in the image
+    layout.  Window 7x7, so H and W must be multiples of 7 (no padding), and
+    0 <= shift < 7.  bf16/fp16 on the GPU runs the fused kernels; fp32 and the
+    CPU take the composed route."""
+    if qkv.dim() != 4 or qkv.shape[3] % (3 * heads):
+        raise ValueError(
+            "window_attention: qkv must be [N, H, W, 3*heads*dh], got "
+            f"{tuple(qkv.shape)} for {heads} heads")
+    dh = qkv.shape[3] // (3 * heads)
+    if dh != _WIN_HEAD_DIM:
+        raise ValueError(
+            f"window_attention: the head dim must be {_WIN_HEAD_DIM}, got {dh}")
+    if qkv.shape[1] % WINDOW or qkv.shape[2] % WINDOW:
+        raise ValueError(
+            "window_attention: H and W must be multiples of the window size "
+            f"{WINDOW} (no padding), got {qkv.shape[1]}x{qkv.shape[2]}")
+    if not 0 <= shift < WINDOW:
+        raise ValueError(
+            f"window_attention: shift must be in [0, {WINDOW}), got {shift}")
+    if tuple(bias_table.shape) != (169, heads):
+        raise ValueError(
+            "window_attention: bias_table must be [169, heads], got "
+            f"{tuple(bias_table.shape)}")
+    if use_native(qkv) and qkv.dtype in (torch.bfloat16, torch.float16):
+        return _WindowAttentionFn.apply(
+            qkv, bias_table, heads, int(shift), float(scale))
+    return _window_attention_composed(qkv, bias_table, heads, int(shift), scale)
+
+
+# ---------------------------------------------------------------------------
 # Dropout / stochastic depth (+ fused residual add), Philox in-kernel
 # ---------------------------------------------------------------------------
 

@@ -197,6 +197,32 @@ class LayerNorm(nn.Module):
         return X.layer_norm(x, self.weight, self.bias, self.eps)
 
 
+class WindowAttention(nn.Module):
+    """Swin's window multi-head attention on an NHWC map [N, H, W, dim]: 7x7
+    windows, cyclically shifted by ``shift`` pixels, with a learned
+    relative-position bias per head (``X.window_attention``)."""
+
+    def __init__(self, dim, heads, shift=0):
+        super().__init__()
+        if dim % heads:
+            raise ValueError("WindowAttention: heads must divide dim")
+        self.dim, self.heads, self.shift = dim, heads, int(shift)
+        self.qkv = Linear(dim, 3 * dim)
+        self.proj = Linear(dim, dim)
+        self.relative_position_bias_table = nn.Parameter(
+            torch.zeros((2 * X.WINDOW - 1) ** 2, heads))
+        nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
+
+    def forward(self, x):
+        out = X.window_attention(
+            self.qkv(x), self.relative_position_bias_table, self.heads,
+            self.shift, (self.dim // self.heads) ** -0.5)
+        return self.proj(out)
+
+    def extra_repr(self):
+        return f"dim={self.dim}, heads={self.heads}, shift={self.shift}"
+
+
 class GlobalAvgPoolNHWC(nn.Module):
     def forward(self, x):
         return X.global_avg_pool_nhwc(x)
