@@ -551,7 +551,29 @@ def train(args, model):
     criterion = _criterion_for(args, train=True)
     batch_mix = getattr(criterion, "mix", None)
     use_master = args.bf16 or args.fp16
-    if args.optimizer == "adamw":
+    if args.trust_ratio:
+        # LARS / LAMB: biases, norm parameters and the model's
+        # no_weight_decay() names get neither decay nor a ratio
+        groups = param_groups_no_decay(model, args.weight_decay)
+        groups[1]["layer_adapt"] = False
+        if args.optimizer == "adamw":
+            optimizer = AdamW(
+                groups,
+                lr=args.learning_rate,
+                betas=(args.adam_beta1, args.adam_beta2),
+                eps=args.adam_epsilon,
+                master_weights=use_master,
+                trust_ratio=True,
+            )
+        else:
+            optimizer = SGD(
+                groups,
+                lr=args.learning_rate,
+                momentum=args.momentum,
+                master_weights=use_master,
+                trust_coef=args.trust_coef,
+            )
+    elif args.optimizer == "adamw":
         optimizer = AdamW(
             param_groups_no_decay(model, args.weight_decay),
             lr=args.learning_rate,
@@ -863,6 +885,15 @@ def build_parser():
                         help="sgd (fused SGD/momentum) | adamw (fused AdamW; "
                              "biases, norm params and the model's "
                              "no_weight_decay() names are not decayed)")
+    parser.add_argument("--trust_ratio", action="store_true",
+                        help="layer-wise trust ratios for large batches: LARS "
+                             "with --optimizer sgd, LAMB with --optimizer "
+                             "adamw; biases, norm params and the model's "
+                             "no_weight_decay() names get neither decay nor "
+                             "a ratio")
+    parser.add_argument("--trust_coef", type=float, default=0.001,
+                        help="LARS's eta (with --trust_ratio and --optimizer "
+                             "sgd; ignored with adamw)")
     parser.add_argument("--adam_beta1", type=float, default=0.9)
     parser.add_argument("--adam_beta2", type=float, default=0.999)
     parser.add_argument("--adam_epsilon", type=float, default=1e-8)

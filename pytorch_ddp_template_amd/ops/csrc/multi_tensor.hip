@@ -5,7 +5,8 @@
 // scale for clip_grad_norm_ (ddp.py:238-239).  Supports bf16 params with
 // fp32 master weights (the apex-O2 slot, ddp.py:165-181, done natively).
 // AdamW (the reference's apex FusedAdam slot) runs on the same
-// machinery with its step count read from a device scalar.
+// machinery with its step count read from a device scalar.  LARS and LAMB
+// add a per-tensor trust ratio to the two rules (norm / ratio / apply).
 //
 // Chunking: tensor lists are flattened into fixed-size chunks dispatched to
 // blocks through a device-side descriptor table, so one launch covers the
@@ -13,7 +14,9 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -263,6 +266,304 @@ __global__ void scale_kernel(const ChunkDesc* __restrict__ chunks,
     p[i] = to_t<T>(to_f(p[i]) * s);
 }
 
+// ---- layer-wise trust ratios: LARS on SGD, LAMB on Adam ----
+// A ratio needs one reduction per tensor that is complete before any element
+// of the tensor moves, so each rule is three launches over the same plan:
+//   norm   one block per chunk: the chunk's two sums of squares, reduced in a
+//          fixed order and written to partial[chunk] with one plain store;
+//   ratio  one wave per tensor: its partials in chunk order (a tensor's
+//          chunks are contiguous in the chunk list) -> ratio[tensor];
+//   apply  one block per chunk: the update, scaled by ratio[tensor].
+// No atomics and no host: every sum has one order, so the ratios are the same
+// bits on every run and on every rank that sees the same gradients.
+struct LayerTable {
+  int first_chunk[kMaxTensors];  // index of the tensor's first chunk
+  int n_chunks[kMaxTensors];
+  float wd[kMaxTensors];   // the tensor's weight decay
+  int adapt[kMaxTensors];  // 0: ratio = 1
+};
+
+struct alignas(8) Sum2 {
+  float a, b;
+};
+
+DEV_INLINE bool step_skipped(const float* __restrict__ guard) {
+  return guard != nullptr && !isfinite(*guard);
+}
+
+// Both sums of a 256-thread block: the xor butterfly inside each wave, then
+// the four wave sums left to right.  Valid in every thread.
+DEV_INLINE Sum2 block_sum2(float a, float b, float* lds /*8*/) {
+  a = wave_reduce_sum(a);
+  b = wave_reduce_sum(b);
+  if (lane_id() == 0) {
+    lds[2 * wave_id()] = a;
+    lds[2 * wave_id() + 1] = b;
+  }
+  __syncthreads();
+  Sum2 s;
+  s.a = ((lds[0] + lds[2]) + lds[4]) + lds[6];
+  s.b = ((lds[1] + lds[3]) + lds[5]) + lds[7];
+  return s;
+}
+
+// What every chunk kernel below needs from the tables.
+template <typename T>
+struct ChunkView {
+  int tensor;
+  long long base, vend, end;
+  const T* g;
+  T* p;
+  float* m;
+  float* v;
+  float* mw;
+  DEV_INLINE ChunkView(const ChunkDesc* __restrict__ chunks,
+                       const PtrTable* __restrict__ tab) {
+    const ChunkDesc d = chunks[blockIdx.x];
+    tensor = d.tensor;
+    base = d.off;
+    end = min(tab->numel[d.tensor], base + (long long)kChunk);
+    vend = base + ((end - base) & ~3LL);
+    g = reinterpret_cast<const T*>(tab->grad[d.tensor]);
+    p = reinterpret_cast<T*>(tab->param[d.tensor]);
+    m = tab->mom[d.tensor];
+    v = tab->aux[d.tensor];
+    mw = tab->master[d.tensor];
+  }
+};
+
+template <typename T>
+__global__ void lars_norm_kernel(const ChunkDesc* __restrict__ chunks,
+                                 const PtrTable* __restrict__ tab,
+                                 const LayerTable* __restrict__ lay,
+                                 Sum2* __restrict__ partial,
+                                 const float* __restrict__ guard) {
+  __shared__ float lds[8];
+  if (step_skipped(guard)) return;
+  const ChunkView<T> c(chunks, tab);
+  // a tensor that does not adapt is not read: its ratio is 1 by the table
+  if (!lay->adapt[c.tensor]) return;
+  float gg = 0.f, ww = 0.f;
+  for (long long i = c.base + (long long)threadIdx.x * 4; i < c.vend;
+       i += (long long)blockDim.x * 4) {
+    Q4<T> g4 = *reinterpret_cast<const Q4<T>*>(c.g + i);
+    F4 w4;
+    Q4<T> p4;
+    if (c.mw) w4 = *reinterpret_cast<const F4*>(c.mw + i);
+    if (!c.mw) p4 = *reinterpret_cast<const Q4<T>*>(c.p + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gf = to_f(g4.v[j]);
+      float w = c.mw ? w4.v[j] : to_f(p4.v[j]);
+      gg += gf * gf;
+      ww += w * w;
+    }
+  }
+  for (long long i = c.vend + threadIdx.x; i < c.end; i += blockDim.x) {
+    float gf = to_f(c.g[i]);
+    float w = c.mw ? c.mw[i] : to_f(c.p[i]);
+    gg += gf * gf;
+    ww += w * w;
+  }
+  Sum2 s = block_sum2(gg, ww, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// One wave per tensor, four tensors per block.  kLamb: partial = (|w|^2,
+// |u|^2), ratio = |w| / |u|; else partial = (|g|^2, |w|^2) and
+// ratio = eta * |w| / (|g| + wd * |w|).  Either is 1 where a norm is zero or
+// the tensor does not adapt.
+template <bool kLamb>
+__global__ void layer_ratio_kernel(const LayerTable* __restrict__ lay,
+                                   const Sum2* __restrict__ partial,
+                                   float* __restrict__ ratio, int n_tensors,
+                                   float eta,
+                                   const float* __restrict__ guard) {
+  if (step_skipped(guard)) return;
+  const int t = blockIdx.x * (blockDim.x / kWave) + wave_id();
+  if (t >= n_tensors) return;
+  float r = 1.f;
+  if (lay->adapt[t]) {
+    const int first = lay->first_chunk[t];
+    const int n = lay->n_chunks[t];
+    float a = 0.f, b = 0.f;
+    for (int k = lane_id(); k < n; k += kWave) {
+      Sum2 s = partial[first + k];
+      a += s.a;
+      b += s.b;
+    }
+    a = sqrtf(wave_reduce_sum(a));
+    b = sqrtf(wave_reduce_sum(b));
+    if (a > 0.f && b > 0.f)
+      r = kLamb ? a / b : eta * b / (a + lay->wd[t] * b);
+  }
+  if (lane_id() == 0) ratio[t] = r;
+}
+
+template <typename T>
+__global__ void lars_apply_kernel(const ChunkDesc* __restrict__ chunks,
+                                  const PtrTable* __restrict__ tab,
+                                  const LayerTable* __restrict__ lay,
+                                  const float* __restrict__ ratio, float lr,
+                                  float momentum, float damp, int nesterov,
+                                  int use_mom,
+                                  const float* __restrict__ guard,
+                                  const float* __restrict__ lr_dev) {
+  if (lr_dev != nullptr) lr = *lr_dev;
+  if (step_skipped(guard)) return;
+  const ChunkView<T> c(chunks, tab);
+  const float r = ratio[c.tensor];
+  const float wd = lay->wd[c.tensor];
+  const float omd = 1.f - damp;
+  auto update = [&](float w, float gf, float& mv) {
+    float d = r * (gf + wd * w);
+    if (use_mom) {
+      mv = momentum * mv + omd * d;
+      d = nesterov ? d + momentum * mv : mv;
+    }
+    return w - lr * d;
+  };
+  for (long long i = c.base + (long long)threadIdx.x * 4; i < c.vend;
+       i += (long long)blockDim.x * 4) {
+    Q4<T> g4 = *reinterpret_cast<const Q4<T>*>(c.g + i);
+    F4 w4, m4;
+    Q4<T> p4;
+    if (c.mw) w4 = *reinterpret_cast<const F4*>(c.mw + i);
+    if (!c.mw) p4 = *reinterpret_cast<const Q4<T>*>(c.p + i);
+    if (use_mom) m4 = *reinterpret_cast<const F4*>(c.m + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float w = update(c.mw ? w4.v[j] : to_f(p4.v[j]), to_f(g4.v[j]), m4.v[j]);
+      w4.v[j] = w;
+      p4.v[j] = to_t<T>(w);
+    }
+    if (use_mom) *reinterpret_cast<F4*>(c.m + i) = m4;
+    if (c.mw) *reinterpret_cast<F4*>(c.mw + i) = w4;
+    *reinterpret_cast<Q4<T>*>(c.p + i) = p4;
+  }
+  for (long long i = c.vend + threadIdx.x; i < c.end; i += blockDim.x) {
+    float mv = use_mom ? c.m[i] : 0.f;
+    float w = update(c.mw ? c.mw[i] : to_f(c.p[i]), to_f(c.g[i]), mv);
+    if (use_mom) c.m[i] = mv;
+    if (c.mw) c.mw[i] = w;
+    c.p[i] = to_t<T>(w);
+  }
+}
+
+// LAMB's per-launch constants; 1 - beta^t as in adamw_kernel.
+struct LambCoef {
+  float b1, omb1, b2, omb2;
+  float inv_bc1;   // 1 / (1 - beta1^t)
+  float sqrt_bc2;  // sqrt(1 - beta2^t)
+  float eps;
+  DEV_INLINE LambCoef(float b1_, float omb1_, float log_b1, float b2_,
+                      float omb2_, float log_b2, float eps_, float t)
+      : b1(b1_), omb1(omb1_), b2(b2_), omb2(omb2_),
+        inv_bc1(1.f / -expm1f(t * log_b1)),
+        sqrt_bc2(sqrtf(-expm1f(t * log_b2))), eps(eps_) {}
+};
+
+// u = m_hat / (sqrt(v_hat) + eps) + wd * w.  The norm pass and the apply pass
+// both form it here from the stored m and v: storing u instead would move as
+// many bytes and cost an fp32 buffer the size of the parameters.
+DEV_INLINE float lamb_u(float m, float v, float w, float wd,
+                        const LambCoef& c) {
+  return (m * c.inv_bc1) / (sqrtf(v) / c.sqrt_bc2 + c.eps) + wd * w;
+}
+
+template <typename T>
+__global__ void lamb_norm_kernel(const ChunkDesc* __restrict__ chunks,
+                                 const PtrTable* __restrict__ tab,
+                                 const LayerTable* __restrict__ lay,
+                                 Sum2* __restrict__ partial, float b1,
+                                 float omb1, float log_b1, float b2,
+                                 float omb2, float log_b2, float eps,
+                                 const float* __restrict__ step,
+                                 const float* __restrict__ guard) {
+  __shared__ float lds[8];
+  if (step_skipped(guard)) return;
+  const LambCoef k(b1, omb1, log_b1, b2, omb2, log_b2, eps, *step);
+  const ChunkView<T> c(chunks, tab);
+  const float wd = lay->wd[c.tensor];
+  float ww = 0.f, uu = 0.f;
+  auto moments = [&](float w, float gf, float& m, float& v) {
+    m = k.b1 * m + k.omb1 * gf;
+    v = k.b2 * v + k.omb2 * gf * gf;
+    float u = lamb_u(m, v, w, wd, k);
+    ww += w * w;
+    uu += u * u;
+  };
+  for (long long i = c.base + (long long)threadIdx.x * 4; i < c.vend;
+       i += (long long)blockDim.x * 4) {
+    Q4<T> g4 = *reinterpret_cast<const Q4<T>*>(c.g + i);
+    F4 w4;
+    Q4<T> p4;
+    if (c.mw) w4 = *reinterpret_cast<const F4*>(c.mw + i);
+    if (!c.mw) p4 = *reinterpret_cast<const Q4<T>*>(c.p + i);
+    F4 m4 = *reinterpret_cast<const F4*>(c.m + i);
+    F4 v4 = *reinterpret_cast<const F4*>(c.v + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      moments(c.mw ? w4.v[j] : to_f(p4.v[j]), to_f(g4.v[j]), m4.v[j],
+              v4.v[j]);
+    *reinterpret_cast<F4*>(c.m + i) = m4;
+    *reinterpret_cast<F4*>(c.v + i) = v4;
+  }
+  for (long long i = c.vend + threadIdx.x; i < c.end; i += blockDim.x) {
+    float mi = c.m[i], vi = c.v[i];
+    moments(c.mw ? c.mw[i] : to_f(c.p[i]), to_f(c.g[i]), mi, vi);
+    c.m[i] = mi;
+    c.v[i] = vi;
+  }
+  // the moments move whether or not the tensor adapts; its sums are read
+  // only if it does
+  if (!lay->adapt[c.tensor]) return;
+  Sum2 s = block_sum2(ww, uu, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+template <typename T>
+__global__ void lamb_apply_kernel(const ChunkDesc* __restrict__ chunks,
+                                  const PtrTable* __restrict__ tab,
+                                  const LayerTable* __restrict__ lay,
+                                  const float* __restrict__ ratio, float lr,
+                                  float b1, float omb1, float log_b1,
+                                  float b2, float omb2, float log_b2,
+                                  float eps, const float* __restrict__ step,
+                                  const float* __restrict__ guard,
+                                  const float* __restrict__ lr_dev) {
+  if (lr_dev != nullptr) lr = *lr_dev;
+  if (step_skipped(guard)) return;
+  const LambCoef k(b1, omb1, log_b1, b2, omb2, log_b2, eps, *step);
+  const ChunkView<T> c(chunks, tab);
+  const float wd = lay->wd[c.tensor];
+  const float lr_r = lr * ratio[c.tensor];
+  for (long long i = c.base + (long long)threadIdx.x * 4; i < c.vend;
+       i += (long long)blockDim.x * 4) {
+    F4 w4;
+    Q4<T> p4;
+    if (c.mw) w4 = *reinterpret_cast<const F4*>(c.mw + i);
+    if (!c.mw) p4 = *reinterpret_cast<const Q4<T>*>(c.p + i);
+    F4 m4 = *reinterpret_cast<const F4*>(c.m + i);
+    F4 v4 = *reinterpret_cast<const F4*>(c.v + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float w = c.mw ? w4.v[j] : to_f(p4.v[j]);
+      w -= lr_r * lamb_u(m4.v[j], v4.v[j], w, wd, k);
+      w4.v[j] = w;
+      p4.v[j] = to_t<T>(w);
+    }
+    if (c.mw) *reinterpret_cast<F4*>(c.mw + i) = w4;
+    *reinterpret_cast<Q4<T>*>(c.p + i) = p4;
+  }
+  for (long long i = c.vend + threadIdx.x; i < c.end; i += blockDim.x) {
+    float w = c.mw ? c.mw[i] : to_f(c.p[i]);
+    w -= lr_r * lamb_u(c.m[i], c.v[i], w, wd, k);
+    if (c.mw) c.mw[i] = w;
+    c.p[i] = to_t<T>(w);
+  }
+}
+
 }  // namespace mt
 
 // ======================= host side =======================================
@@ -275,6 +576,14 @@ struct LaunchPlan {
   torch::Tensor chunks_host;  // PINNED sources kept alive: a hipGraph-
   torch::Tensor table_host;   // captured H2D copy replays from this memory
   int n_blocks;
+  int n_tensors;
+  // layer-wise steps only (add_layer_state): they live as long as the
+  // tables, so a captured step replays against the same pointers
+  torch::Tensor layer_dev;   // LayerTable
+  torch::Tensor layer_host;  // its pinned source
+  torch::Tensor partial;     // Sum2[n_blocks]
+  torch::Tensor ratio;       // float[n_tensors], created as ones
+  bool adapt = false;        // false: ratio is never written and stays 1
 };
 
 // Plan cache: the descriptor tables depend only on the tensor PTRS/numels,
@@ -338,10 +647,71 @@ std::vector<LaunchPlan> make_plans(const std::vector<torch::Tensor>& ref,
     plan.chunks_dev = plan.chunks_host.to(dev, /*non_blocking=*/true);
     plan.table_dev = plan.table_host.to(dev, /*non_blocking=*/true);
     plan.n_blocks = (int)chunks.size();
+    plan.n_tensors = (int)(t_end - t);
     plans.push_back(plan);
     t = t_end;
   }
   return plans;
+}
+
+// Give each plan what a layer-wise step needs on top of the tables: where
+// each tensor's chunks lie in the chunk list (read back from the list
+// itself), its weight decay and whether it adapts, and the buffers for the
+// chunk sums and the ratios.  A tensor never spans plans, so neither does
+// its norm.
+std::vector<LaunchPlan> add_layer_state(std::vector<LaunchPlan> plans,
+                                        const torch::Device& dev, float wd,
+                                        bool adapt) {
+  for (auto& plan : plans) {
+    plan.layer_host = torch::empty(
+        {(long long)sizeof(mt::LayerTable)},
+        torch::dtype(torch::kUInt8).pinned_memory(true));
+    auto* lay = reinterpret_cast<mt::LayerTable*>(plan.layer_host.data_ptr());
+    for (int i = 0; i < mt::kMaxTensors; ++i) {
+      lay->first_chunk[i] = 0;
+      lay->n_chunks[i] = 0;
+      lay->wd[i] = wd;
+      lay->adapt[i] = adapt ? 1 : 0;
+    }
+    auto* chunks =
+        reinterpret_cast<const mt::ChunkDesc*>(plan.chunks_host.data_ptr());
+    for (int k = 0; k < plan.n_blocks; ++k) {
+      const int tensor = chunks[k].tensor;
+      TORCH_CHECK(tensor >= 0 && tensor < plan.n_tensors);
+      if (lay->n_chunks[tensor]++ == 0) lay->first_chunk[tensor] = k;
+      TORCH_CHECK(lay->first_chunk[tensor] + lay->n_chunks[tensor] == k + 1,
+                  "a tensor's chunks must be contiguous in the chunk list");
+    }
+    plan.layer_dev = plan.layer_host.to(dev, /*non_blocking=*/true);
+    auto f32 = torch::dtype(torch::kFloat32).device(dev);
+    plan.partial = torch::zeros({std::max(plan.n_blocks, 1), 2}, f32);
+    plan.ratio = torch::ones({plan.n_tensors}, f32);
+    plan.adapt = adapt;
+  }
+  return plans;
+}
+
+// The three launches of one layer-wise step over one plan; norm and apply
+// are given the plan's pointers and launch their kernel.  A plan whose group
+// does not adapt keeps the ones its ratios were created with: it skips the
+// ratio launch, and LARS, whose norm pass writes nothing else, that one too.
+template <bool kLamb, typename Norm, typename Apply>
+void launch_layer_step(const LaunchPlan& plan, hipStream_t stream, float eta,
+                       const float* guard, Norm norm, Apply apply) {
+  if (plan.n_blocks == 0) return;
+  auto* chunks =
+      reinterpret_cast<const mt::ChunkDesc*>(plan.chunks_dev.data_ptr());
+  auto* tab = reinterpret_cast<const mt::PtrTable*>(plan.table_dev.data_ptr());
+  auto* lay =
+      reinterpret_cast<const mt::LayerTable*>(plan.layer_dev.data_ptr());
+  auto* partial = reinterpret_cast<mt::Sum2*>(plan.partial.data_ptr());
+  float* ratio = plan.ratio.data_ptr<float>();
+  if (kLamb || plan.adapt) norm(chunks, tab, lay, partial);
+  if (plan.adapt)
+    hipLaunchKernelGGL((mt::layer_ratio_kernel<kLamb>),
+                       dim3((plan.n_tensors + 3) / 4), dim3(256), 0, stream,
+                       lay, partial, ratio, plan.n_tensors, eta, guard);
+  apply(chunks, tab, lay, ratio);
 }
 
 }  // namespace
@@ -509,6 +879,214 @@ void adamw_step(std::vector<torch::Tensor> params,
           (float)lr, (float)beta1, (float)(1.0 - beta1), log_b1, (float)beta2,
           (float)(1.0 - beta2), log_b2, (float)eps, (float)wd, step_p, guard_p,
           lr_p);
+    });
+  }
+}
+
+// ---- layer-wise steps: LARS (optim.SGD, trust_coef > 0) and LAMB
+// (optim.AdamW, trust_ratio=True).  One call is one param group of one dtype:
+// lr, momentum / betas and eps are the group's, and so are wd and adapt,
+// which travel per tensor in the plan's LayerTable and are part of its key.
+// Neither ticks skip_count: the optimizers do that once per step().
+namespace {
+
+struct LayerArgs {
+  torch::Device dev;
+  torch::ScalarType dtype;
+  const float* guard = nullptr;
+  const float* lr = nullptr;
+  std::vector<float*> master;
+
+  // checks shared by both steps; f32_state checks one state list
+  LayerArgs(const char* op, const std::vector<torch::Tensor>& params,
+            const std::vector<torch::Tensor>& grads,
+            const std::vector<torch::Tensor>& masters,
+            const c10::optional<torch::Tensor>& guard_t,
+            const c10::optional<torch::Tensor>& lr_t)
+      : dev(torch::kCPU), dtype(torch::kFloat32), op_(op) {
+    TORCH_CHECK(!params.empty(), op_, ": empty parameter list");
+    TORCH_CHECK(grads.size() == params.size() &&
+                    masters.size() == params.size(),
+                op_, ": list lengths differ");
+    dev = params[0].device();
+    dtype = params[0].scalar_type();
+    if (guard_t.has_value()) guard = scalar(*guard_t, "guard");
+    if (lr_t.has_value()) lr = scalar(*lr_t, "lr_tensor");
+    for (size_t i = 0; i < params.size(); ++i) {
+      TORCH_CHECK(params[i].scalar_type() == dtype &&
+                      grads[i].scalar_type() == dtype,
+                  op_, ": param/grad ", i, " dtype differs from params[0]");
+      TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous() &&
+                      grads[i].numel() == params[i].numel() &&
+                      params[i].device() == dev && grads[i].device() == dev,
+                  op_, ": param/grad ", i,
+                  " must be contiguous, of one numel, on params[0]'s device");
+    }
+    master = f32_state(params, masters, "masters", /*optional=*/true);
+  }
+
+  const float* scalar(const torch::Tensor& t, const char* what) const {
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == 1 &&
+                    t.device() == dev,
+                op_, ": ", what,
+                " must be a one-element f32 tensor on the params' device");
+    return t.data_ptr<float>();
+  }
+
+  std::vector<float*> f32_state(const std::vector<torch::Tensor>& params,
+                                const std::vector<torch::Tensor>& ts,
+                                const char* what, bool optional) const {
+    TORCH_CHECK(ts.size() == params.size(), op_, ": list lengths differ");
+    std::vector<float*> out(ts.size(), nullptr);
+    for (size_t i = 0; i < ts.size(); ++i) {
+      if (optional && !(ts[i].defined() && ts[i].numel())) continue;
+      TORCH_CHECK(ts[i].scalar_type() == torch::kFloat32 &&
+                      ts[i].is_contiguous() &&
+                      ts[i].numel() == params[i].numel() &&
+                      ts[i].device() == dev,
+                  op_, ": ", what, "[", i,
+                  "] must be contiguous f32 with the param's numel");
+      out[i] = ts[i].data_ptr<float>();
+    }
+    return out;
+  }
+
+ private:
+  const char* op_;
+};
+
+const void* float_bits(float v) {
+  uint32_t u;
+  std::memcpy(&u, &v, sizeof u);
+  return (const void*)(uintptr_t)u;
+}
+
+}  // namespace
+
+void lars_step(std::vector<torch::Tensor> params,
+               std::vector<torch::Tensor> grads,
+               std::vector<torch::Tensor> moms,
+               std::vector<torch::Tensor> masters, double lr, double momentum,
+               double wd, double damp, bool nesterov, double trust_coef,
+               bool adapt, c10::optional<torch::Tensor> guard,
+               c10::optional<torch::Tensor> lr_tensor) {
+  const LayerArgs a("lars_step", params, grads, masters, guard, lr_tensor);
+  TORCH_CHECK(trust_coef > 0.0 || !adapt,
+              "lars_step: a group that adapts needs trust_coef > 0");
+  const bool use_mom = momentum != 0.0;
+  const auto m_p = a.f32_state(params, moms, "moms", /*optional=*/!use_mom);
+  const size_t n = params.size();
+  PlanKey key;
+  key.ptrs.reserve(5 * n + 4);
+  key.ptrs.push_back((const void*)0x1A25);  // op tag
+  key.ptrs.push_back((const void*)(uintptr_t)n);
+  key.ptrs.push_back(float_bits((float)wd));
+  key.ptrs.push_back((const void*)(uintptr_t)adapt);
+  for (size_t i = 0; i < n; ++i) {
+    key.ptrs.push_back(params[i].data_ptr());
+    key.ptrs.push_back(grads[i].data_ptr());
+    key.ptrs.push_back((const void*)(uintptr_t)params[i].numel());
+    key.ptrs.push_back(use_mom ? m_p[i] : nullptr);
+    key.ptrs.push_back(a.master[i]);
+  }
+  const auto& plans = cached_plans(std::move(key), [&] {
+    return add_layer_state(
+        make_plans(params, a.dev,
+                   [&](size_t i, int local, mt::PtrTable* tab) {
+                     tab->grad[local] = grads[i].data_ptr();
+                     tab->param[local] = params[i].data_ptr();
+                     tab->mom[local] = use_mom ? m_p[i] : nullptr;
+                     tab->aux[local] = nullptr;
+                     tab->master[local] = a.master[i];
+                   }),
+        a.dev, (float)wd, adapt);
+  });
+  auto stream = c10::hip::getCurrentHIPStream();
+  for (auto& plan : plans) {
+    DDP_DISPATCH_FLOAT(a.dtype, "lars_step", [&] {
+      launch_layer_step</*kLamb=*/false>(
+          plan, stream, (float)trust_coef, a.guard,
+          [&](auto chunks, auto tab, auto lay, auto partial) {
+            hipLaunchKernelGGL((mt::lars_norm_kernel<scalar_t>),
+                               dim3(plan.n_blocks), dim3(256), 0, stream,
+                               chunks, tab, lay, partial, a.guard);
+          },
+          [&](auto chunks, auto tab, auto lay, auto ratio) {
+            hipLaunchKernelGGL((mt::lars_apply_kernel<scalar_t>),
+                               dim3(plan.n_blocks), dim3(256), 0, stream,
+                               chunks, tab, lay, ratio, (float)lr,
+                               (float)momentum, (float)damp, nesterov ? 1 : 0,
+                               use_mom ? 1 : 0, a.guard, a.lr);
+          });
+    });
+  }
+}
+
+// `step` is the optimizer's device step count, already advanced for this
+// step by the caller, as for adamw_step.
+void lamb_step(std::vector<torch::Tensor> params,
+               std::vector<torch::Tensor> grads,
+               std::vector<torch::Tensor> exp_avgs,
+               std::vector<torch::Tensor> exp_avg_sqs,
+               std::vector<torch::Tensor> masters, double lr, double beta1,
+               double beta2, double eps, double wd, bool adapt,
+               torch::Tensor step, c10::optional<torch::Tensor> guard,
+               c10::optional<torch::Tensor> lr_tensor) {
+  const LayerArgs a("lamb_step", params, grads, masters, guard, lr_tensor);
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "lamb_step: betas must be in [0, 1)");
+  const float* step_p = a.scalar(step, "step");
+  const auto m_p = a.f32_state(params, exp_avgs, "exp_avgs", false);
+  const auto v_p = a.f32_state(params, exp_avg_sqs, "exp_avg_sqs", false);
+  const size_t n = params.size();
+  PlanKey key;
+  key.ptrs.reserve(6 * n + 4);
+  key.ptrs.push_back((const void*)0x1A3B);  // op tag
+  key.ptrs.push_back((const void*)(uintptr_t)n);
+  key.ptrs.push_back(float_bits((float)wd));
+  key.ptrs.push_back((const void*)(uintptr_t)adapt);
+  for (size_t i = 0; i < n; ++i) {
+    key.ptrs.push_back(params[i].data_ptr());
+    key.ptrs.push_back(grads[i].data_ptr());
+    key.ptrs.push_back((const void*)(uintptr_t)params[i].numel());
+    key.ptrs.push_back(m_p[i]);
+    key.ptrs.push_back(v_p[i]);
+    key.ptrs.push_back(a.master[i]);
+  }
+  const auto& plans = cached_plans(std::move(key), [&] {
+    return add_layer_state(
+        make_plans(params, a.dev,
+                   [&](size_t i, int local, mt::PtrTable* tab) {
+                     tab->grad[local] = grads[i].data_ptr();
+                     tab->param[local] = params[i].data_ptr();
+                     tab->mom[local] = m_p[i];
+                     tab->aux[local] = v_p[i];
+                     tab->master[local] = a.master[i];
+                   }),
+        a.dev, (float)wd, adapt);
+  });
+  const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1);
+  const float b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
+  const float log_b1 = (float)std::log(beta1);
+  const float log_b2 = (float)std::log(beta2);
+  auto stream = c10::hip::getCurrentHIPStream();
+  for (auto& plan : plans) {
+    DDP_DISPATCH_FLOAT(a.dtype, "lamb_step", [&] {
+      launch_layer_step</*kLamb=*/true>(
+          plan, stream, 0.f, a.guard,
+          [&](auto chunks, auto tab, auto lay, auto partial) {
+            hipLaunchKernelGGL((mt::lamb_norm_kernel<scalar_t>),
+                               dim3(plan.n_blocks), dim3(256), 0, stream,
+                               chunks, tab, lay, partial, b1, omb1, log_b1,
+                               b2, omb2, log_b2, (float)eps, step_p, a.guard);
+          },
+          [&](auto chunks, auto tab, auto lay, auto ratio) {
+            hipLaunchKernelGGL((mt::lamb_apply_kernel<scalar_t>),
+                               dim3(plan.n_blocks), dim3(256), 0, stream,
+                               chunks, tab, lay, ratio, (float)lr, b1, omb1,
+                               log_b1, b2, omb2, log_b2, (float)eps, step_p,
+                               a.guard, a.lr);
+          });
     });
   }
 }

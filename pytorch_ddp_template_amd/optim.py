@@ -9,6 +9,11 @@
   with fp32 master weights, the device-side overflow skip and the
   device-scalar lr of ``SGD``; ``param_groups_no_decay`` builds its usual
   two groups (no decay on biases, norm params and names the model excludes).
+* Layer-wise trust ratios for large batches: ``SGD(trust_coef=eta)`` is LARS
+  and ``AdamW(trust_ratio=True)`` is LAMB.  Each is three multi-tensor
+  launches (chunk sums, one ratio per tensor, update) with no atomics and no
+  host read, so the ratios are bit-identical from run to run and across
+  ranks.  A group with ``layer_adapt=False`` keeps ratio 1.
 * ``clip_grad_norm_`` — global L2 norm + scale (reference ddp.py:238-239)
   via the multi-tensor l2norm/scale kernels.
 * ``get_linear_schedule_with_warmup`` — linear warmup then linear decay to 0
@@ -75,7 +80,10 @@ class SGD(torch.optim.Optimizer):
         dampening: float = 0.0,
         nesterov: bool = False,
         master_weights: bool = False,
+        trust_coef: float = 0.0,
     ):
+        if trust_coef < 0.0:
+            raise ValueError(f"trust_coef must be >= 0: {trust_coef}")
         defaults = dict(
             lr=lr,
             momentum=momentum,
@@ -83,6 +91,8 @@ class SGD(torch.optim.Optimizer):
             dampening=dampening,
             nesterov=nesterov,
             master_weights=master_weights,
+            trust_coef=trust_coef,
+            layer_adapt=True,
         )
         super().__init__(params, defaults)
 
@@ -122,6 +132,15 @@ class SGD(torch.optim.Optimizer):
                 loss = closure()
         self._guard, self._skip_count = guard, skip_count
         self._lr_tensor = lr_tensor
+        # LARS: every group goes through the layer-wise kernels (a group that
+        # does not adapt has ratio 1); they never touch the skip counter, so
+        # it ticks here, once per step, with capture-legal torch ops
+        self._lars = any(
+            g.get("trust_coef", 0.0) > 0 for g in self.param_groups
+        )
+        if self._lars and guard is not None and skip_count is not None:
+            skipped = 1 - torch.isfinite(guard).float().reshape(())
+            skip_count += skipped.reshape(skip_count.shape)
         for group in self.param_groups:
             params, grads, moms, masters = [], [], [], []
             momentum = group["momentum"]
@@ -142,9 +161,63 @@ class SGD(torch.optim.Optimizer):
                 masters.append(state.get("master") if use_master else None)
             if not params:
                 continue
-            self._fused_step(group, params, grads, moms, masters)
+            if self._lars:
+                self._lars_step(group, params, grads, moms, masters)
+            else:
+                self._fused_step(group, params, grads, moms, masters)
         self._guard = self._skip_count = self._lr_tensor = None
         return loss
+
+    def _lars_step(self, group, params, grads, moms, masters):
+        """LARS: ``r = eta * |w| / (|g| + wd * |w|)`` per tensor (1 where a
+        norm is zero or the group does not adapt), ``d = r * (g + wd * w)``,
+        then SGD's momentum rule on ``d``."""
+        lr = group["lr"]
+        momentum = group["momentum"]
+        wd = group["weight_decay"]
+        damp = group["dampening"]
+        nesterov = group["nesterov"]
+        eta = group.get("trust_coef", 0.0)
+        adapt = bool(group.get("layer_adapt", True)) and eta > 0
+        if use_native(*params):
+            native().lars_step(
+                params,
+                grads,
+                [m if m is not None else torch.Tensor() for m in moms],
+                [m if m is not None else torch.Tensor() for m in masters],
+                lr,
+                momentum,
+                wd,
+                damp,
+                nesterov,
+                eta,
+                adapt,
+                self._guard,
+                self._lr_tensor,
+            )
+            return
+        # CPU path, fp32 (also the calibration partner of the kernels)
+        if self._guard is not None and not bool(
+            torch.isfinite(self._guard).all()
+        ):
+            return
+        if self._lr_tensor is not None:
+            lr = float(self._lr_tensor)
+        for p, g, m, mw in zip(params, grads, moms, masters):
+            w = mw if mw is not None else p.float()
+            gf = g.float()
+            r = 1.0
+            if adapt:
+                wn, gn = w.norm(), gf.norm()
+                if wn > 0 and gn > 0:
+                    r = eta * wn / (gn + wd * wn)
+            d = gf.add(w, alpha=wd).mul_(r)
+            if momentum != 0:
+                m.mul_(momentum).add_(d, alpha=1 - damp)
+                d = d.add(m, alpha=momentum) if nesterov else m
+            w.add_(d, alpha=-lr)
+            if w is not p:
+                p.copy_(w.to(p.dtype))
 
     def _fused_step(self, group, params, grads, moms, masters):
         lr = group["lr"]
@@ -223,6 +296,7 @@ class AdamW(torch.optim.Optimizer):
         eps: float = 1e-8,
         weight_decay: float = 1e-2,
         master_weights: bool = False,
+        trust_ratio: bool = False,
     ):
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"betas must be in [0, 1): {betas}")
@@ -232,6 +306,8 @@ class AdamW(torch.optim.Optimizer):
             eps=eps,
             weight_decay=weight_decay,
             master_weights=master_weights,
+            trust_ratio=trust_ratio,
+            layer_adapt=True,
         )
         super().__init__(params, defaults)
         self._step_t = None  # f32 device scalar, created on the first step
@@ -339,6 +415,12 @@ class AdamW(torch.optim.Optimizer):
         beta1, beta2 = group["betas"]
         eps = group["eps"]
         wd = group["weight_decay"]
+        if group.get("trust_ratio", False):
+            self._lamb_step(
+                group, params, grads, ms, vs, masters, step_t, guard,
+                lr_tensor,
+            )
+            return
         if use_native(*params):
             native().adamw_step(
                 params,
@@ -376,6 +458,59 @@ class AdamW(torch.optim.Optimizer):
             v.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
             denom = (v.sqrt() / bc2_sqrt).add_(eps)
             w.addcdiv_(m, denom, value=-step_size)
+            if w is not p:
+                p.copy_(w.to(p.dtype))
+
+    def _lamb_step(self, group, params, grads, ms, vs, masters, step_t,
+                   guard, lr_tensor):
+        """LAMB: Adam's moments, ``u = m_hat / (sqrt(v_hat) + eps) + wd * w``
+        (the decay inside ``u``, not decoupled), ``r = |w| / |u|`` per tensor
+        (1 where a norm is zero or the group does not adapt) and
+        ``w -= lr * r * u``."""
+        lr = group["lr"]
+        beta1, beta2 = group["betas"]
+        eps = group["eps"]
+        wd = group["weight_decay"]
+        adapt = bool(group.get("layer_adapt", True))
+        if use_native(*params):
+            native().lamb_step(
+                params,
+                grads,
+                ms,
+                vs,
+                [m if m is not None else torch.Tensor() for m in masters],
+                lr,
+                beta1,
+                beta2,
+                eps,
+                wd,
+                adapt,
+                step_t,
+                guard,
+                lr_tensor,
+            )
+            return
+        # CPU path, fp32 (also the calibration partner of the kernels)
+        if guard is not None and not bool(torch.isfinite(guard).all()):
+            return
+        if lr_tensor is not None:
+            lr = float(lr_tensor)
+        t = float(step_t)
+        bc1 = 1 - beta1 ** t
+        bc2_sqrt = (1 - beta2 ** t) ** 0.5
+        for p, g, m, v, mw in zip(params, grads, ms, vs, masters):
+            w = mw if mw is not None else p.float()
+            gf = g.float()
+            m.lerp_(gf, 1 - beta1)
+            v.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
+            denom = (v.sqrt() / bc2_sqrt).add_(eps)
+            u = (m / bc1).div_(denom).add_(w, alpha=wd)
+            r = 1.0
+            if adapt:
+                wn, un = w.norm(), u.norm()
+                if wn > 0 and un > 0:
+                    r = wn / un
+            w.sub_(u.mul_(r), alpha=lr)
             if w is not p:
                 p.copy_(w.to(p.dtype))
 
