@@ -22,7 +22,7 @@ from __future__ import annotations
 from torch import nn
 
 from ..ops import GELU, Conv2dNHWC, GlobalAvgPoolNHWC, LayerNorm, Linear
-from ..ops.functional import dropout_add
+from ..ops.functional import dropout_add, mlp_gelu
 
 
 class Block(nn.Module):
@@ -36,10 +36,13 @@ class Block(nn.Module):
         self.pwconv2 = Linear(4 * dim, dim)
 
     def forward(self, x):
-        h = self.pwconv2(self.act(self.pwconv1(self.norm(self.dwconv(x)))))
-        if self.training and self.p_path > 0:
-            return dropout_add(h, x, 0.0, self.p_path, True)
-        return x + h
+        # one mlp_gelu call on the two Linears' parameters; the plain add
+        # goes into it (pwconv2's epilogue where the width is eligible)
+        path = self.training and self.p_path > 0
+        h = mlp_gelu(self.norm(self.dwconv(x)), self.pwconv1.weight,
+                     self.pwconv1.bias, self.pwconv2.weight,
+                     self.pwconv2.bias, None if path else x)
+        return dropout_add(h, x, 0.0, self.p_path, True) if path else h
 
 
 class ConvNeXt(nn.Module):

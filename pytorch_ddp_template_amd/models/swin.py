@@ -30,7 +30,7 @@ from __future__ import annotations
 from torch import nn
 
 from ..ops import GELU, GlobalAvgPoolNHWC, LayerNorm, Linear, WindowAttention
-from ..ops.functional import WINDOW, dropout_add
+from ..ops.functional import WINDOW, dropout_add, mlp_gelu
 
 _EPS = 1e-5
 
@@ -55,7 +55,13 @@ class Block(nn.Module):
 
     def forward(self, x):
         x = self._residual(self.attn(self.norm1(x)), x)
-        return self._residual(self.mlp(self.norm2(x)), x)
+        # one mlp_gelu call on the Sequential's parameters; the plain add
+        # goes into it (fc2's epilogue where the width is eligible)
+        fc1, fc2 = self.mlp[0], self.mlp[2]
+        path = self.training and self.p_path > 0
+        h = mlp_gelu(self.norm2(x), fc1.weight, fc1.bias, fc2.weight,
+                     fc2.bias, None if path else x)
+        return dropout_add(h, x, 0.0, self.p_path, True) if path else h
 
 
 class PatchMerging(nn.Module):

@@ -25,6 +25,12 @@ the fused route it happens inside the flash forward and backward kernels (the
 probabilities never exist in memory; both kernels regenerate the mask); the
 composed route applies the same mask to the materialized probabilities.
 
+The MLP is one ``mlp_gelu`` call, composed from ``linear`` / ``gelu`` by
+default; with ``PDT_MLP_FUSED=1`` bias+GELU, the GELU-backward multiply and
+the bias+residual add run in GEMM epilogues when the widths are multiples of
+256 in bf16 on the GPU.  With ``dropout > 0`` in training the members are
+called one by one, as the dropout sits between GELU and the second Linear.
+
 Not covered: fusing the post-GELU dropout into the GELU kernel.  (Label
 smoothing and mixup / cutmix live outside the model: ``ops.BatchMix`` and
 ``ops.CrossEntropyLoss``.)
@@ -38,7 +44,9 @@ import torch
 from torch import nn
 
 from ..ops import GELU, LayerNorm, Linear
-from ..ops.functional import attention, attention_qkv, dropout, dropout_add
+from ..ops.functional import (
+    attention, attention_qkv, dropout, dropout_add, mlp_gelu,
+)
 from ..ops.native import native_available
 
 
@@ -90,14 +98,23 @@ class Block(nn.Module):
             Linear(dim * mlp_ratio, dim),
         )
 
+    def _mlp(self, x, residual):
+        # the Sequential keeps the state_dict keys; its Linears' parameters
+        # feed the epilogue-fused MLP (composed where it is not eligible)
+        fc1, fc2 = self.mlp[0], self.mlp[2]
+        return mlp_gelu(x, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                        residual)
+
     def forward(self, x):
         if not self.training or (self.p == 0 and self.p_path == 0):
             x = x + self.attn(self.norm1(x))
-            x = x + self.mlp(self.norm2(x))
-            return x
-        # mlp's members are called one by one (the Sequential keeps its
-        # state_dict keys); each residual is one dropout_add
+            return self._mlp(self.norm2(x), x)
+        # each residual is one dropout_add
         x = dropout_add(self.attn(self.norm1(x)), x, self.p, self.p_path, True)
+        if self.p == 0:
+            return dropout_add(self._mlp(self.norm2(x), None), x, 0.0,
+                               self.p_path, True)
+        # dropout after the GELU: mlp's members are called one by one
         h = self.mlp[1](self.mlp[0](self.norm2(x)))
         h = self.mlp[2](dropout(h, self.p, True))
         return dropout_add(h, x, self.p, self.p_path, True)

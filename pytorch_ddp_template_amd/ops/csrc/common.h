@@ -58,6 +58,24 @@ DEV_INLINE short f2bfbits(float f) {
   return (short)(rounded >> 16);
 }
 
+// GELU and its derivative: ONE definition for the elementwise kernels
+// (gelu_fwd / gelu_bwd) and the GEMM epilogues of gemm_plain.hip, which must
+// agree with them bit for bit.
+namespace ew {
+struct GeluOp {  // exact erf form (matches torch F.gelu default)
+  DEV_INLINE float operator()(float a) const {
+    return 0.5f * a * (1.f + erff(a * 0.70710678118654752440f));
+  }
+};
+struct GeluBwdOp {  // (dy, x) -> dy * (Phi(x) + x phi(x))
+  DEV_INLINE float operator()(float dy, float x) const {
+    float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
+    float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
+    return dy * (cdf + x * pdf);
+  }
+};
+}  // namespace ew
+
 // grid-stride loop helper
 #define GRID_STRIDE(i, n)                                              \
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; \

@@ -21,11 +21,6 @@ namespace ew {
 struct ReluOp {
   DEV_INLINE float operator()(float a) const { return fmaxf(a, 0.f); }
 };
-struct GeluOp {  // exact erf form (matches torch F.gelu default)
-  DEV_INLINE float operator()(float a) const {
-    return 0.5f * a * (1.f + erff(a * 0.70710678118654752440f));
-  }
-};
 
 template <typename T, typename Op>
 __global__ void unary_kernel(const T* __restrict__ in, T* __restrict__ out,
@@ -79,13 +74,6 @@ struct AddOp {
 struct ReluBwdOp {  // (dy, y) -> dy * (y > 0)
   DEV_INLINE float operator()(float dy, float y) const {
     return y > 0.f ? dy : 0.f;
-  }
-};
-struct GeluBwdOp {  // (dy, x) -> dy * (Phi(x) + x phi(x))
-  DEV_INLINE float operator()(float dy, float x) const {
-    float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
-    float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
-    return dy * (cdf + x * pdf);
   }
 };
 

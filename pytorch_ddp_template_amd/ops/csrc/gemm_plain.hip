@@ -17,7 +17,9 @@
 //     BEFORE the current tile's MFMAs, so their latency hides under the
 //     64 MFMAs; the barrier's implicit vmcnt(0) drains them after.
 //   * Epilogue: accumulators staged through LDS (reusing the operand
-//     buffers) so C is written in coalesced 16B rows.
+//     buffers) so C is written in coalesced 16B rows; the transformer-MLP
+//     fusions (bias+GELU with both outputs, GELU-backward multiply,
+//     bias+residual) work on those row chunks (enum Epi below).
 // The K-slot XOR swizzle (T2) is applied on the glds SOURCE address with
 // the matching XOR on the ds_read side: rows 4..7 (mod 8) swap 32B halves
 // of each 64B k-span, taking the b128 fragment reads from 8-way to 4-way
@@ -49,11 +51,35 @@ __device__ __forceinline__ int kswz(int row, int kbyte) {
   return kbyte ^ (((row >> 2) & 1) << 5);
 }
 
-template <bool HAS_BIAS, bool RELU>
+// Epilogue kinds.  The first four are the plain kernel's; the last three are
+// the transformer-MLP fusions (host entry gemm_nt_epi):
+//   BIAS_GELU_DUAL  fc1 forward: C = y = bf16(acc + bias) and C2 = g =
+//                   bf16(gelu(float(y))).  g is computed in the write-out
+//                   phase from the staged 16B chunk of y, so the tile is
+//                   staged once and g is gelu_fwd(y) bit for bit.
+//   MUL_DGELU       fc2 data gradient: C = bf16(float(bf16(acc)) *
+//                   gelu'(float(aux))), aux = fc1's y, read in the write-out
+//                   phase with the store's own coalesced 16B row chunks.
+//   BIAS_RES        fc2 forward: C = bf16(acc + bias + float(aux)), aux = the
+//                   residual.  ONE rounding of the sum, so the tile is staged
+//                   in f32: the 128 KiB LDS holds half a tile, two rounds.
+enum Epi {
+  EPI_NONE, EPI_RELU, EPI_BIAS, EPI_BIAS_RELU,
+  EPI_BIAS_GELU_DUAL, EPI_MUL_DGELU, EPI_BIAS_RES
+};
+
+// Any M >= 1: rows at or beyond M in the last tile are staged from row M-1
+// (the glds source stays inside A) and never stored; aux reads are masked
+// the same way.
+template <int EPI>
 __global__ __launch_bounds__(THREADS, 1) void gemm_nt_plain256_kernel(
     const __hip_bfloat16* __restrict__ A, const __hip_bfloat16* __restrict__ B,
     __hip_bfloat16* __restrict__ C, const __hip_bfloat16* __restrict__ bias,
+    const __hip_bfloat16* __restrict__ aux, __hip_bfloat16* __restrict__ C2,
     int M, int N, int K) {
+  constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU ||
+                            EPI == EPI_BIAS_GELU_DUAL || EPI == EPI_BIAS_RES;
+  constexpr bool RELU = EPI == EPI_RELU || EPI == EPI_BIAS_RELU;
   // one shared object only (hipcc de-pipelines glds with a second one)
   __shared__ __hip_bfloat16 smem[NT_BUF * 2 * BM * BK];
 
@@ -90,7 +116,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_nt_plain256_kernel(
       // (8 lanes per 128B row) because BK*2B == 128B.
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
-              A + (long long)(m0 + row) * K + kk),
+              A + (long long)min(m0 + row, M - 1) * K + kk),
           (__attribute__((address_space(3))) unsigned int*)(
               sa + (r * 64 + wave * 8) * BK),
           16, 0, 0);
@@ -169,29 +195,87 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_nt_plain256_kernel(
     for (int ni = 0; ni < 4; ++ni)
       bv[ni] = bf2f(bias[n0 + wn + ni * 16 + (lane & 15)]);
   }
-  __hip_bfloat16* cs = smem;  // [256][256] bf16 view = 128 KiB
+  // write-out: 512 threads cover 16 rows x 32 16B-chunks per round
+  const int wrow = tid >> 5, wchunk = tid & 31;
+
+  if constexpr (EPI == EPI_BIAS_RES) {
+    // f32 staging, half a tile per round: round h takes each wave's m-frags
+    // 4h..4h+3, i.e. tile rows [0,64)+64h of the upper waves and
+    // [128,192)+64h of the lower ones, as LDS rows [0,64) and [64,128).
+    float* cf = reinterpret_cast<float*>(smem);  // [128][256] f32 = 128 KiB
 #pragma unroll
-  for (int mi = 0; mi < 8; ++mi)
+    for (int h = 0; h < 2; ++h) {
+      if (h) __syncthreads();  // round 0 is read out before it is overwritten
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int col = wn + ni * 16 + (lane & 15);
+      for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int row = wm + mi * 16 + (lane >> 4) * 4 + reg;
-        float v = acc[mi][ni][reg];
-        if (HAS_BIAS) v += bv[ni];
-        if (RELU) v = fmaxf(v, 0.f);
-        cs[row * BN + col] = f2bf(v);
+        for (int ni = 0; ni < 4; ++ni) {
+          const int col = wn + ni * 16 + (lane & 15);
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const int lrow = (wave >> 2) * 64 + mi * 16 + (lane >> 4) * 4 + reg;
+            cf[lrow * BN + col] = acc[h * 4 + mi][ni][reg] + bv[ni];
+          }
+        }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int lrow = r * 16 + wrow;
+        const int grow = m0 + (lrow >> 6) * 128 + h * 64 + (lrow & 63);
+        if (grow < M) {
+          const long long off = (long long)grow * N + n0 + wchunk * 8;
+          const float* s = cf + lrow * BN + wchunk * 8;
+          const float4v lo = *(const float4v*)s, hi = *(const float4v*)(s + 4);
+          const short8 rv = *(const short8*)(aux + off);
+          short8 o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            o[j] = f2bfbits(lo[j] + bfbits2f(rv[j]));
+            o[4 + j] = f2bfbits(hi[j] + bfbits2f(rv[4 + j]));
+          }
+          *(short8*)(C + off) = o;
+        }
       }
     }
-  __syncthreads();
-  // 512 threads write 256 rows x 512B: 16 rows per round, 32 chunks/row
-  const int wrow = tid >> 5, wchunk = tid & 31;
+  } else {
+    __hip_bfloat16* cs = smem;  // [256][256] bf16 view = 128 KiB
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = r * 16 + wrow;
-    *(short8*)((char*)(C + (long long)(m0 + row) * N + n0) + wchunk * 16) =
-        *(const short8*)((const char*)(cs + row * BN) + wchunk * 16);
+    for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int col = wn + ni * 16 + (lane & 15);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int row = wm + mi * 16 + (lane >> 4) * 4 + reg;
+          float v = acc[mi][ni][reg];
+          if (HAS_BIAS) v += bv[ni];
+          if (RELU) v = fmaxf(v, 0.f);
+          cs[row * BN + col] = f2bf(v);
+        }
+      }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = r * 16 + wrow;
+      if (m0 + row < M) {
+        const long long off = (long long)(m0 + row) * N + n0 + wchunk * 8;
+        short8 v = *(const short8*)(cs + row * BN + wchunk * 8);
+        if constexpr (EPI == EPI_MUL_DGELU) {
+          const short8 yv = *(const short8*)(aux + off);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[j] = f2bfbits(ew::GeluBwdOp{}(bfbits2f(v[j]), bfbits2f(yv[j])));
+        }
+        *(short8*)(C + off) = v;
+        if constexpr (EPI == EPI_BIAS_GELU_DUAL) {
+          // the conversions of gelu_fwd's VecIO<bf16>, so g == gelu_fwd(y)
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[j] = f2bfbits(ew::GeluOp{}(bfbits2f(v[j])));
+          *(short8*)(C2 + off) = v;
+        }
+      }
+    }
   }
 }
 
@@ -337,14 +421,80 @@ bool gemm_nt_plain256(const torch::Tensor& A, const torch::Tensor& B,
   auto stream = c10::hip::getCurrentHIPStream();
   dim3 grid(N / gp::BN, M / gp::BM);
   const bf16* bias_p = bias.has_value() ? ptr16<bf16>(*bias) : nullptr;
-  auto kern = bias_p ? (relu ? &gp::gemm_nt_plain256_kernel<true, true>
-                            : &gp::gemm_nt_plain256_kernel<true, false>)
-                     : (relu ? &gp::gemm_nt_plain256_kernel<false, true>
-                            : &gp::gemm_nt_plain256_kernel<false, false>);
+  auto kern =
+      bias_p ? (relu ? &gp::gemm_nt_plain256_kernel<gp::EPI_BIAS_RELU>
+                     : &gp::gemm_nt_plain256_kernel<gp::EPI_BIAS>)
+             : (relu ? &gp::gemm_nt_plain256_kernel<gp::EPI_RELU>
+                     : &gp::gemm_nt_plain256_kernel<gp::EPI_NONE>);
   hipLaunchKernelGGL(kern, grid, dim3(gp::THREADS), 0, stream,
                      ptr16<bf16>(A), ptr16<bf16>(B), ptr16<bf16>(C), bias_p,
-                     M, N, K);
+                     (const bf16*)nullptr, (bf16*)nullptr, M, N, K);
   return true;
+}
+
+// The MLP epilogue kinds of the 256x256 kernel: (C, C2) from A [M,K],
+// B [N,K], any M >= 1, N % 256 == 0, K % 64 == 0, bf16.
+//   "bias_gelu": C = A B^T + bias, C2 = gelu(C)          (aux unused)
+//   "mul_dgelu": C = (A B^T) * gelu'(aux), aux [M,N]     (bias unused)
+//   "bias_res":  C = A B^T + bias + aux, aux [M,N]
+// C2 is an empty tensor except for "bias_gelu".  No M floor and no library
+// route: an unsupported dtype or shape is an error.
+std::vector<torch::Tensor> gemm_nt_epi(torch::Tensor A, torch::Tensor B,
+                                       c10::optional<torch::Tensor> bias,
+                                       const std::string& kind,
+                                       c10::optional<torch::Tensor> aux) {
+  const int epi = kind == "bias_gelu"   ? gp::EPI_BIAS_GELU_DUAL
+                  : kind == "mul_dgelu" ? gp::EPI_MUL_DGELU
+                  : kind == "bias_res"  ? gp::EPI_BIAS_RES
+                                        : -1;
+  TORCH_CHECK(epi >= 0, "gemm_nt_epi: unknown kind '", kind,
+              "' (bias_gelu, mul_dgelu, bias_res)");
+  auto ok16 = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() &&
+           t.scalar_type() == torch::kBFloat16;
+  };
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && ok16(A) && ok16(B),
+              "gemm_nt_epi: A and B must be contiguous 2-D bf16 GPU tensors");
+  const long long M = A.size(0), K = A.size(1), N = B.size(0);
+  TORCH_CHECK(B.size(1) == K, "gemm_nt_epi: K mismatch");
+  TORCH_CHECK(M >= 1 && N >= gp::BN && N % gp::BN == 0 && K >= gp::BK &&
+                  K % gp::BK == 0,
+              "gemm_nt_epi needs M >= 1, N % 256 == 0, K % 64 == 0; got M=", M,
+              " N=", N, " K=", K);
+  const long long tiles_m = (M + gp::BM - 1) / gp::BM;
+  TORCH_CHECK(tiles_m <= 65535 && N < (1LL << 24) && K < (1LL << 24),
+              "gemm_nt_epi: shape too large for the launch grid");
+  const bool want_bias = epi != gp::EPI_MUL_DGELU;
+  const bool want_aux = epi != gp::EPI_BIAS_GELU_DUAL;
+  TORCH_CHECK(bias.has_value() == want_bias && aux.has_value() == want_aux,
+              "gemm_nt_epi: kind '", kind, "' takes ",
+              want_bias ? "a bias" : "no bias", " and ",
+              want_aux ? "an aux tensor" : "no aux tensor");
+  if (want_bias)
+    TORCH_CHECK(ok16(*bias) && bias->dim() == 1 && bias->size(0) == N,
+                "gemm_nt_epi: bias must be a bf16 GPU vector of N elements");
+  if (want_aux)
+    TORCH_CHECK(ok16(*aux) && aux->dim() == 2 && aux->size(0) == M &&
+                    aux->size(1) == N,
+                "gemm_nt_epi: aux must be a contiguous bf16 GPU [M, N] tensor");
+  auto C = torch::empty({M, N}, A.options());
+  auto C2 = epi == gp::EPI_BIAS_GELU_DUAL ? torch::empty({M, N}, A.options())
+                                          : torch::empty({0}, A.options());
+  auto kern = epi == gp::EPI_BIAS_GELU_DUAL
+                  ? &gp::gemm_nt_plain256_kernel<gp::EPI_BIAS_GELU_DUAL>
+              : epi == gp::EPI_MUL_DGELU
+                  ? &gp::gemm_nt_plain256_kernel<gp::EPI_MUL_DGELU>
+                  : &gp::gemm_nt_plain256_kernel<gp::EPI_BIAS_RES>;
+  dim3 grid((unsigned)(N / gp::BN), (unsigned)tiles_m);
+  hipLaunchKernelGGL(kern, grid, dim3(gp::THREADS), 0,
+                     c10::hip::getCurrentHIPStream(), ptr16<bf16>(A),
+                     ptr16<bf16>(B), ptr16<bf16>(C),
+                     want_bias ? ptr16<bf16>(*bias) : (const bf16*)nullptr,
+                     want_aux ? ptr16<bf16>(*aux) : (const bf16*)nullptr,
+                     epi == gp::EPI_BIAS_GELU_DUAL ? ptr16<bf16>(C2)
+                                                   : (bf16*)nullptr,
+                     (int)M, (int)N, (int)K);
+  return {C, C2};
 }
 
 // dw[I][J] (fp32, pre-zeroed by caller semantics: allocated here) from

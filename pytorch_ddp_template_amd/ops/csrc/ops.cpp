@@ -37,6 +37,11 @@ torch::Tensor bmm_nt_bf16(torch::Tensor A, torch::Tensor B,
 // transposed-operand split-K NT (gemm_plain.hip): dw = A[I,M] @ B[J,M]^T,
 // fp32 out, for linear/1x1-conv weight grads routed via explicit transposes
 torch::Tensor gemm_nt_splitk_f32(torch::Tensor A, torch::Tensor B);
+// MLP epilogue kinds of the 256x256 NT kernel (gemm_plain.hip)
+std::vector<torch::Tensor> gemm_nt_epi(torch::Tensor A, torch::Tensor B,
+                                       c10::optional<torch::Tensor> bias,
+                                       const std::string& kind,
+                                       c10::optional<torch::Tensor> aux);
 torch::Tensor bmm_tn_bf16(torch::Tensor A, torch::Tensor B);
 std::vector<torch::Tensor> bmm_tn_bias_bf16(torch::Tensor A, torch::Tensor B);
 torch::Tensor conv2d_fwd_bf16(torch::Tensor x, torch::Tensor w,
@@ -408,6 +413,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_f32") = false);
   m.def("gemm_tn", &gemm_tn);
   m.def("gemm_nt_splitk_f32", &gemm_nt_splitk_f32);
+  m.def("gemm_nt_epi", &gemm_nt_epi, py::arg("A"), py::arg("B"),
+        py::arg("bias"), py::arg("kind"), py::arg("aux"));
   m.def("gemm_tn_bias", [](torch::Tensor A, torch::Tensor B) {
     TORCH_CHECK(A.scalar_type() == torch::kBFloat16 ||
                 A.scalar_type() == torch::kHalf,

@@ -819,6 +819,85 @@ def gelu(x):
 
 
 # ---------------------------------------------------------------------------
+# Transformer MLP: Linear -> GELU -> Linear (+ residual), GEMM-epilogue fused
+# ---------------------------------------------------------------------------
+
+
+class _MlpGeluFn(torch.autograd.Function):
+    """The MLP on the epilogue kinds of the 256x256 NT kernel
+    (``gemm_nt_epi``, ops/csrc/gemm_plain.hip): fc1 writes y = x w1^T + b1 and
+    g = gelu(y) from one tile, fc2 adds bias and residual as it stores, and
+    fc2's data gradient is multiplied by gelu'(y) as it stores, so no GELU,
+    GELU-backward or add pass runs over the activations.  No host reads."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, residual):
+        ext = native()
+        xs = x.reshape(-1, x.shape[-1]).contiguous()
+        w1, w2 = w1.contiguous(), w2.contiguous()
+        y, g = ext.gemm_nt_epi(xs, w1, b1, "bias_gelu", None)
+        if residual is None:
+            out = ext.gemm_nt(g, w2, b2, False, False)
+        else:
+            res = residual.reshape(-1, w2.shape[0]).contiguous()
+            out, _ = ext.gemm_nt_epi(g, w2, b2, "bias_res", res)
+        ctx.save_for_backward(xs, y, g, w1, w2)
+        ctx.has_res = residual is not None
+        return out.reshape(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, dout):
+        xs, y, g, w1, w2 = ctx.saved_tensors
+        ext = native()
+        douts = dout.reshape(-1, dout.shape[-1]).contiguous()
+        dz, _ = ext.gemm_nt_epi(
+            douts, ext.transpose2d(w2), None, "mul_dgelu", y)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.gemm_nt(dz, ext.transpose2d(w1), None, False, False)
+            dx = dx.reshape(*dout.shape[:-1], w1.shape[1])
+        # bias grads ride inside the TN GEMMs (dy is staged anyway)
+        dw2, db2 = ext.gemm_tn_bias(douts, g)
+        dw1, db1 = ext.gemm_tn_bias(dz, xs)
+        dres = dout if ctx.has_res and ctx.needs_input_grad[5] else None
+        return (dx, dw1.to(w1.dtype), db1.to(w1.dtype), dw2.to(w2.dtype),
+                db2.to(w2.dtype), dres)
+
+
+def _mlp_fused_ok(x, w1, b1, w2, b2, residual) -> bool:
+    # off unless PDT_MLP_FUSED=1: measured slower than the library GEMM plus
+    # the separate pass at the ViT-B shapes (profiles/r18_mlp_gelu.md)
+    if os.environ.get("PDT_MLP_FUSED", "0") != "1":
+        return False
+    if b1 is None or b2 is None:
+        return False
+    ts = [x, w1, b1, w2, b2] + ([] if residual is None else [residual])
+    if not use_native(*ts) or any(t.dtype != torch.bfloat16 for t in ts):
+        return False
+    hidden, c = w1.shape
+    c_out = w2.shape[0]
+    return (hidden % 256 == 0 and c % 256 == 0 and c_out % 256 == 0
+            and w2.shape[1] == hidden and x.shape[-1] == c and x.numel() > 0
+            and (residual is None
+                 or residual.shape == (*x.shape[:-1], c_out)))
+
+
+def mlp_gelu(x, w1, b1, w2, b2, residual=None):
+    """(residual +) linear(gelu(linear(x, w1, b1)), w2, b2); x (..., C),
+    w1 (H, C), w2 (C_out, H).
+
+    With ``PDT_MLP_FUSED=1`` (read per call), bf16 on the GPU with H, C and
+    C_out multiples of 256 runs the epilogue-fused GEMMs above; everything
+    else (the default, CPU, fp16, fp32, other widths, a missing bias) is
+    composed from ``linear`` / ``gelu`` and a plain add, so the function is
+    total."""
+    if _mlp_fused_ok(x, w1, b1, w2, b2, residual):
+        return _MlpGeluFn.apply(x, w1, b1, w2, b2, residual)
+    h = linear(gelu(linear(x, w1, b1)), w2, b2)
+    return h if residual is None else residual + h
+
+
+# ---------------------------------------------------------------------------
 # Batched GEMM + softmax + attention (ViT path)
 # ---------------------------------------------------------------------------
 
